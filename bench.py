@@ -26,6 +26,16 @@ timed region.  N=1 renders whole frames one after another on one stream.
 
 Rank 0 prints ONE JSON line.  Rays are counted by the kernel (primary + shadow
 rays actually cast) — the counts equal the CPU oracle's (tests/test_gpu_parity).
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line (metric, value, ms_per_step, the workload's config).  `--full` adds,
+after the timed steps, everything else the bench measures or checks: the
+roofline, the CPU baseline, the `secondary` configs, the scene rebuild time,
+the tile path's per-rank timings and its frame against a whole-frame render.
+`--dump-outputs DIR` writes the frame the last timed step produced to
+DIR/frame.npy (float32, (height, width, 4); a seeded pixel sample above
+64 MB); the scene, the pose and the sampling are seeded, so two builds run
+with the same arguments can be compared value for value.
 """
 from __future__ import annotations
 
@@ -63,7 +73,7 @@ def parse(argv=None):
     ap.add_argument("--config", default="c3")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="target CPU-baseline sample duration")
+                    help="--full: target CPU-baseline sample duration")
     ap.add_argument("--variant", type=int, default=0, help="scene-kernel variant (0 = default)")
     ap.add_argument("--shard", default="",
                     help="R/N: render only rank R's tiles of an N-way split on this one GPU "
@@ -81,7 +91,7 @@ def parse(argv=None):
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (with --backend gloo)")
     ap.add_argument("--secondary", default="c2,c5,c5d",
-                    help="N=1 only: also time these configs (a few frames each) and report them "
+                    help="--full, N=1 only: also time these configs (a few frames each) and report them "
                          "under `secondary`; '' to skip")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_latest.json"),
                     help="PMC traffic summary written by tools/pmc_traffic.py")
@@ -91,7 +101,36 @@ def parse(argv=None):
                          "path the reference's Displayer calls; the default without a launcher at N > 1")
     ap.add_argument("--transport", default="auto", choices=("auto", "rccl", "peer"),
                     help="--native: slab transport (auto = RCCL for distinct devices)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: "
+                         "the roofline, the CPU baseline (--cpu-baseline), the other configs "
+                         "(--secondary), the scene rebuild time, the tile path's per-rank timings and "
+                         "its frame against a whole-frame render")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the frame the last timed step produced to DIR/frame.npy (float32)")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20240607   # which pixels of a larger frame are kept
+
+
+def dump_outputs(path: str, rgba8, width: int, height: int) -> None:
+    """--dump-outputs: the RGBA8 frame a caller of the timed path receives,
+    as DIR/frame.npy in float32, shape (height, width, 4).  A frame over the
+    budget (4K) is cut to a fixed, seeded sample of its pixels, shape (n, 4),
+    in ascending pixel order."""
+    import numpy as np
+
+    px = np.asarray(rgba8, dtype=np.uint8).reshape(height * width, 4)
+    keep = DUMP_BUDGET_BYTES // 16
+    if px.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], keep, replace=False))
+        out = px[idx].astype(np.float32)
+    else:
+        out = px.astype(np.float32).reshape(height, width, 4)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frame.npy"), out)
 
 
 class stdout_to_stderr:
@@ -443,7 +482,8 @@ def run_native(args) -> int:
     r.resize(W, H)
     r.setPosition(pose)
     info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
-    rebuild = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    rebuild = (r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+               if args.full else None)
     st = r.render(stats=True)  # counters summed over the devices (equal to the oracle's)
     rays_frame = st.primary_rays + st.shadow_rays
     for _ in range(args.warmup):
@@ -460,7 +500,50 @@ def run_native(args) -> int:
     r.synchronize()
     elapsed = time.perf_counter() - t0
     ev_ms = e0.elapsed_time(e1)
-    # outside the timed region: per-device times of single frames (the
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r.readback(), W, H)
+    mi = r.multi_info()
+    value = rays_frame * args.steps / elapsed / 1e6
+    out = {
+        "metric": f"Mrays/s (primary+shadow) at {W}x{H}, {cfg.spp} spp, {cfg.n_spheres} spheres",
+        "value": round(value, 3),
+        "unit": "Mrays/s",
+        "n_gpus": n,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded spheres, SURVEY.md 8d)",
+        "config": {
+            "workload": f"{cfg.name}: {cfg.note}",
+            "width": W, "height": H, "spp": cfg.spp, "n_spheres": cfg.n_spheres,
+            "octree_depth": info["max_depth"], "octree_nodes": info["n_nodes"],
+            "prim_refs": info["n_prim_refs"], "leaf_capacity": cfg.leaf_capacity,
+            "parallelism": f"native-tiles{ts}x{n}",
+            "launch": "native: one process, rt_create_multi over devices " + str(mi["devices"]),
+            "transport": mi["transport"],
+            "devices_seen": seen,
+            "frames_in_flight": mi["frames_in_flight"],
+            "rays_per_frame": int(rays_frame),
+            "primary_per_frame": int(st.primary_rays), "shadow_per_frame": int(st.shadow_rays),
+            "wall_ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "event_ms_per_step": round(ev_ms / args.steps, 4),
+            "scene_build_ms": round(info["build_ms"], 1),
+            "scene_upload_ms": round(info["upload_ms"], 1),
+        },
+        "cpu_baseline": None,
+    }
+    if args.same_device:
+        out["config"]["note"] = ("rehearsal: every device is GPU 0, so the per-device render times "
+                                 "include the other devices' kernels")
+    if not args.full:
+        r.close()
+        print(json.dumps(out), flush=True)
+        return 0
+    # --full, outside the timed region: per-device times of single frames (the
     # handle waits after each), the frame against one renderer's whole frame,
     # and devices[0]'s own tiles rendered alone for its counters
     per = []
@@ -498,47 +581,13 @@ def run_native(args) -> int:
     roof["time_source"] = ("devices[0]'s render of its tiles, HIP events on its render stream "
                            "(rt_get_multi_timing, median of 5 single frames)")
     roof["per_ray"] = {"nodes": s0.nodes_visited / rays0, "prims": s0.prims_tested / rays0}
-    value = rays_frame * args.steps / elapsed / 1e6
-    out = {
-        "metric": f"Mrays/s (primary+shadow) at {W}x{H}, {cfg.spp} spp, {cfg.n_spheres} spheres",
-        "value": round(value, 3),
-        "unit": "Mrays/s",
-        "n_gpus": n,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded spheres, SURVEY.md 8d)",
-        "config": {
-            "workload": f"{cfg.name}: {cfg.note}",
-            "width": W, "height": H, "spp": cfg.spp, "n_spheres": cfg.n_spheres,
-            "octree_depth": info["max_depth"], "octree_nodes": info["n_nodes"],
-            "prim_refs": info["n_prim_refs"], "leaf_capacity": cfg.leaf_capacity,
-            "parallelism": f"native-tiles{ts}x{n}",
-            "launch": "native: one process, rt_create_multi over devices " + str(mi["devices"]),
-            "transport": mi["transport"],
-            "devices_seen": seen,
-            "frames_in_flight": mi["frames_in_flight"],
-            "rays_per_frame": int(rays_frame),
-            "primary_per_frame": int(st.primary_rays), "shadow_per_frame": int(st.shadow_rays),
-            "wall_ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "event_ms_per_step": round(ev_ms / args.steps, 4),
-            "device_render_ms": [round(x, 4) for x in render_ms],
-            "deliver_ms": round(deliver_ms, 4),
-            "tiles_frame_check": frame_ok,
-            "scene_build_ms": round(info["build_ms"], 1),
-            "scene_rebuild_ms": round(rebuild["build_ms"], 2),
-            "scene_upload_ms": round(info["upload_ms"], 1),
-        },
-        "roofline": roof,
-        "cpu_baseline": None,
-    }
-    if args.same_device:
-        out["config"]["note"] = ("rehearsal: every device is GPU 0, so the per-device render times "
-                                 "include the other devices' kernels")
+    out["config"].update({
+        "device_render_ms": [round(x, 4) for x in render_ms],
+        "deliver_ms": round(deliver_ms, 4),
+        "tiles_frame_check": frame_ok,
+        "scene_rebuild_ms": round(rebuild["build_ms"], 2),
+    })
+    out["roofline"] = roof
     print(json.dumps(out), flush=True)
     return 0 if frame_ok else 1
 
@@ -593,7 +642,8 @@ def main():
     info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
     # the same scene again: a rebuild into the buffers the first build sized
     # (the per-frame cost of a dynamic scene; the first build also allocates)
-    rebuild = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    rebuild = (r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+               if args.full else None)
     _, K = r.camera()
 
     dev = torch.device("cuda", local)
@@ -708,8 +758,15 @@ def main():
     elapsed = time.perf_counter() - t0
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in events])) if events else float("nan")
+    if args.dump_outputs and rank == 0:
+        last = max(args.steps - 1, 0) % F  # the slot the last timed step wrote
+        if args.shard:  # no gather: the caller holds this rank's packed tiles
+            tiles = slabs[last].cpu().numpy()
+            dump_outputs(args.dump_outputs, tiles, ts, tiles.size // (4 * ts))
+        else:
+            dump_outputs(args.dump_outputs, frames[last].cpu().numpy(), W, H)
     tile_report = None
-    if tiled and not args.shard:
+    if args.full and tiled and not args.shard:
         # VERDICT r03 item 4, outside the timed region: per-rank render and
         # gather+unpack spans of the timed frames, this rank's tiles rendered
         # alone (one frame at a time), rank 0's whole frame alone
@@ -749,31 +806,6 @@ def main():
 
     if rank == 0:
         value = rays_frame * args.steps / elapsed / 1e6
-        # roofline of the dominant kernel on this rank: algorithmic bytes per launch
-        pix = (W * H) if not tiled else len(my_ids) * ts * ts
-        alg_bytes = float(cnt[2].item()) * NODE_BYTES + float(cnt[3].item()) * PRIM_BYTES + pix * PIXEL_BYTES
-        simds = torch.cuda.get_device_properties(dev).multi_processor_count * 4
-        src_id = rt._lib.kernel_source_id()
-        if not tiled:
-            pmc, pmc_note = load_pmc(args.pmc, cfg.name, world, src_id, cfg.leaf_capacity)
-        elif args.shard:
-            pmc, pmc_note = None, "--shard projection: no PMC roofs"
-        else:
-            # the tile path: this rank's launch does its share of the frame's
-            # rays; the N=1 counters projected onto it
-            share = float(cnt[0].item() + cnt[1].item()) / rays_frame
-            pmc, pmc_note = pmc_for_launch(args.pmc, cfg, world, src_id, share)
-        # frames in flight overlap, so one frame's event span is not its share
-        # of the GPU: price a frame per step of wall time instead
-        roof_ms = kern_ms if F == 1 else elapsed / args.steps * 1e3
-        roof = roofline(roof_ms, alg_bytes, pmc, simds, args.pmc, pmc_note)
-        if pmc and pmc.get("valu_lane_util") is not None:
-            roof["valu_lane_util"] = round(pmc["valu_lane_util"], 4)
-        roof["time_ms"] = round(roof_ms, 4)
-        roof["time_source"] = ("kernel HIP events on the launch stream" if F == 1 else
-                               f"wall time per step ({F} frames in flight)")
-        roof["per_ray"] = {"nodes": float(cnt[2].item()) / float(cnt[0].item() + cnt[1].item()),
-                           "prims": float(cnt[3].item()) / float(cnt[0].item() + cnt[1].item())}
         out = {
             "metric": f"Mrays/s (primary+shadow) at {W}x{H}, {cfg.spp} spp, {cfg.n_spheres} spheres",
             "value": round(value, 3),
@@ -802,40 +834,66 @@ def main():
                 "render_span_ms": round(kern_ms, 4),
                 "wall_ms_per_step": round(elapsed / args.steps * 1e3, 4),
                 "scene_build_ms": round(info["build_ms"], 1),
-                "scene_rebuild_ms": round(rebuild["build_ms"], 2),
                 "scene_upload_ms": round(info["upload_ms"], 1),
             },
-            "roofline": roof,
             "cpu_baseline": None,
         }
         if args.shard:
             out["config"]["shard"] = args.shard
             out["metric"] += f" [projection: rank {args.shard} tiles only]"
-        if tiled and not args.shard:
-            # the gathered frame must equal a whole-frame render, byte for byte
-            whole = torch.empty_like(frame)
-            r.render(whole.data_ptr(), sptr)
-            torch.cuda.synchronize(dev)
-            used = frames[:min(F, args.warmup + args.steps)]  # slots that received a frame
-            out["config"]["tiles_frame_check"] = all(bool(torch.equal(whole, f)) for f in used)
-            if tile_report is not None:
-                if args.same_device:
-                    tile_report["note"] = ("rehearsal: every rank on one GPU, so the per-rank times "
-                                           "include the other ranks' kernels")
-                out["config"]["tile_path"] = tile_report
-        if world == 1 and not args.shard and args.secondary:
-            out["secondary"] = {}
-            for name in [c for c in args.secondary.split(",") if c and c != cfg.name]:
+        if args.full:
+            # roofline of the dominant kernel on this rank: algorithmic bytes per launch
+            pix = (W * H) if not tiled else len(my_ids) * ts * ts
+            alg_bytes = float(cnt[2].item()) * NODE_BYTES + float(cnt[3].item()) * PRIM_BYTES + pix * PIXEL_BYTES
+            simds = torch.cuda.get_device_properties(dev).multi_processor_count * 4
+            src_id = rt._lib.kernel_source_id()
+            if not tiled:
+                pmc, pmc_note = load_pmc(args.pmc, cfg.name, world, src_id, cfg.leaf_capacity)
+            elif args.shard:
+                pmc, pmc_note = None, "--shard projection: no PMC roofs"
+            else:
+                # the tile path: this rank's launch does its share of the frame's
+                # rays; the N=1 counters projected onto it
+                share = float(cnt[0].item() + cnt[1].item()) / rays_frame
+                pmc, pmc_note = pmc_for_launch(args.pmc, cfg, world, src_id, share)
+            # frames in flight overlap, so one frame's event span is not its share
+            # of the GPU: price a frame per step of wall time instead
+            roof_ms = kern_ms if F == 1 else elapsed / args.steps * 1e3
+            roof = roofline(roof_ms, alg_bytes, pmc, simds, args.pmc, pmc_note)
+            if pmc and pmc.get("valu_lane_util") is not None:
+                roof["valu_lane_util"] = round(pmc["valu_lane_util"], 4)
+            roof["time_ms"] = round(roof_ms, 4)
+            roof["time_source"] = ("kernel HIP events on the launch stream" if F == 1 else
+                                   f"wall time per step ({F} frames in flight)")
+            roof["per_ray"] = {"nodes": float(cnt[2].item()) / float(cnt[0].item() + cnt[1].item()),
+                               "prims": float(cnt[3].item()) / float(cnt[0].item() + cnt[1].item())}
+            out["config"]["scene_rebuild_ms"] = round(rebuild["build_ms"], 2)
+            out["roofline"] = roof
+            if tiled and not args.shard:
+                # the gathered frame must equal a whole-frame render, byte for byte
+                whole = torch.empty_like(frame)
+                r.render(whole.data_ptr(), sptr)
+                torch.cuda.synchronize(dev)
+                used = frames[:min(F, args.warmup + args.steps)]  # slots that received a frame
+                out["config"]["tiles_frame_check"] = all(bool(torch.equal(whole, f)) for f in used)
+                if tile_report is not None:
+                    if args.same_device:
+                        tile_report["note"] = ("rehearsal: every rank on one GPU, so the per-rank times "
+                                               "include the other ranks' kernels")
+                    out["config"]["tile_path"] = tile_report
+            if world == 1 and not args.shard and args.secondary:
+                out["secondary"] = {}
+                for name in [c for c in args.secondary.split(",") if c and c != cfg.name]:
+                    try:
+                        out["secondary"][name] = secondary_config(rt, torch, name, dev, stream,
+                                                                  pmc_path=args.pmc, simds=simds)
+                    except Exception as e:  # reported, never fatal for the headline
+                        out["secondary"][name] = {"error": repr(e)}
+            if world == 1 and args.cpu_baseline == "auto":
                 try:
-                    out["secondary"][name] = secondary_config(rt, torch, name, dev, stream,
-                                                              pmc_path=args.pmc, simds=simds)
-                except Exception as e:  # reported, never fatal for the headline
-                    out["secondary"][name] = {"error": repr(e)}
-        if world == 1 and args.cpu_baseline == "auto":
-            try:
-                out["cpu_baseline"] = cpu_baseline(cfg, K, pose, args.cpu_seconds)
-            except Exception as e:  # reported, never fatal for the GPU number
-                out["cpu_baseline"] = {"error": repr(e)}
+                    out["cpu_baseline"] = cpu_baseline(cfg, K, pose, args.cpu_seconds)
+                except Exception as e:  # reported, never fatal for the GPU number
+                    out["cpu_baseline"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
     for rr in rs:
         rr.close()

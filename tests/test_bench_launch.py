@@ -57,6 +57,67 @@ def test_more_gpus_than_visible_exits_nonzero():
     assert "visible" in p.stderr and not p.stdout.strip()
 
 
+def test_full_is_off_by_default():
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs == ""
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_frame_within_budget(tmp_path):
+    """--dump-outputs: a frame is written whole as float32 (height, width, 4);
+    one over the 64 MB budget as the same seeded pixel sample every time."""
+    import numpy as np
+    w, h = 7, 5
+    fr = (np.arange(w * h * 4) * 37 % 256).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), fr, w, h)
+    a = np.load(tmp_path / "a" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (h, w, 4)
+    assert np.array_equal(a.reshape(-1), fr.astype(np.float32))
+    w, h = 3840, 2160  # C4: 133 MB as float32
+    big = (np.arange(w * h * 4, dtype=np.uint32) * 2654435761 >> 24).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "b"), big, w, h)
+    bench.dump_outputs(str(tmp_path / "c"), big, w, h)
+    b = np.load(tmp_path / "b" / "frame.npy")
+    assert b.dtype == np.float32 and b.shape[1] == 4 and b.nbytes <= 64 << 20
+    assert np.array_equal(b, np.load(tmp_path / "c" / "frame.npy"))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(w * h, b.shape[0], replace=False))
+    assert np.array_equal(b, big.reshape(-1, 4)[idx].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_headline_and_dumps_last_frame(gpu, tmp_path):
+    """A plain `--gpus 1` run prints the headline line alone (what moved behind
+    --full is absent) and --dump-outputs holds the frame the timed path
+    rendered: the same bytes one renderer gives for the config."""
+    import numpy as np
+    from raytracingstudy_amd.camera import scene_pose
+    p = _run_bench(["--gpus", "1", "--config", "c2", "--steps", "3", "--warmup", "1",
+                    "--dump-outputs", str(tmp_path)], {})
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.strip().splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    c = rt.CONFIGS["c2"]
+    rays = line["config"]["rays_per_frame"]
+    assert line["value"] == pytest.approx(rays / line["ms_per_step"] / 1e3, rel=1e-3)
+    assert line["cpu_baseline"] is None
+    assert "roofline" not in line and "secondary" not in line
+    assert "scene_rebuild_ms" not in line["config"]
+    sp, al = rt.configs.scene_spheres(c, rt.SEED)
+    with rt.KernelRenderer(c.width, c.height, mode="scene", spp=c.spp, device=0,
+                           light_dir=rt.configs.LIGHT_DIR, ambient=rt.configs.AMBIENT) as r:
+        r.resize(c.width, c.height)
+        r.setPosition(scene_pose())
+        r.set_scene(sp, al, max_depth=c.max_depth, leaf_capacity=c.leaf_capacity)
+        r.render()
+        ref = r.readback()
+    got = np.load(tmp_path / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (c.height, c.width, 4)
+    assert np.array_equal(got, ref.reshape(c.height, c.width, 4).astype(np.float32))
+
+
 def _c3_pmc():
     with open(PMC) as f:
         return json.load(f)["c3"]

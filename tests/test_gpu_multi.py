@@ -285,7 +285,7 @@ def test_bench_native_one_device(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--native",
-                        "--config", "c2", "--steps", "5", "--warmup", "2"],
+                        "--full", "--config", "c2", "--steps", "5", "--warmup", "2"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

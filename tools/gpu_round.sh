@@ -31,6 +31,6 @@ tag, cfgs = sys.argv[1], sys.argv[2].split(",")
 m = {c: json.load(open(f"gpurun_out/prof_{tag}_{c}/pmc_summary.json")) for c in cfgs}
 json.dump(m, open(f"gpurun_out/{tag}/pmc_merged.json", "w"), indent=1)
 EOF
-timeout -k 10 400 python -u bench.py --pmc "$OUT/pmc_merged.json" > "$OUT/bench.json" 2> "$OUT/bench.err" ||
+timeout -k 10 400 python -u bench.py --full --pmc "$OUT/pmc_merged.json" > "$OUT/bench.json" 2> "$OUT/bench.err" ||
     { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
