@@ -32,6 +32,10 @@
  *   (none: single device)                                 rt_render_tiles / rt_unpack_tiles
  *   (none: single device; SURVEY 8b B2 "device ids",      rt_create_multi / rt_get_multi_info /
  *     8e E1 ncclCommInitAll)                                rt_get_multi_timing
+ *   (none: Octree::traverse is a stub,                    rt_trace_rays
+ *     include/octree.h:19-21; no ray entry point)
+ *   (none: Octree::traverse is a stub; the Displayer's    rt_pick
+ *     mouse input selects nothing)
  *   (none: no error reporting, all void)                  rt_last_error
  *
  * Threading: one handle per host thread / stream; calls on one handle are not
@@ -299,6 +303,49 @@ void* rt_framebuffer(rt_renderer* r);
  * default stream (src/renderer.cu:149).  Renderers made one after another get
  * streams on different hardware queues, so frames in flight on them overlap. */
 void* rt_stream(rt_renderer* r);
+
+/* ---- ray queries ---------------------------------------------------------- */
+/* Batch ray queries against the scene octree, outside any frame: picking,
+ * line-of-sight and collision tests, lidar-style sweeps, a custom integrator's
+ * secondary rays.  The reference has no counterpart (Octree::traverse is a
+ * stub, include/octree.h:19-21).
+ * A ray is origin + t * dir; `dir` is used as given (the caller normalises it
+ * if t is to be a distance).  A sphere is hit iff its nearest root t with
+ * tmin < t < tmax exists (the frames' own intersection test). */
+typedef struct rt_ray {
+    float origin[3];
+    float tmin;
+    float dir[3];
+    float tmax;
+} rt_ray; /* 32 bytes */
+typedef struct rt_hit {
+    float t;         /* the hit's t; a miss: the ray's tmax                        */
+    uint32_t sphere; /* index into the caller's sphere list; a miss: RT_NO_HIT     */
+} rt_hit; /* 8 bytes */
+#define RT_NO_HIT 0xFFFFFFFFu
+enum {
+    RT_QUERY_NEAREST = 0, /* smallest t, then smallest sphere index                */
+    RT_QUERY_ANY = 1      /* the first accepted sphere in the walk's cell order and
+                             each leaf's list order (an occlusion test)            */
+};
+/* Trace n rays (dev_rays: n rt_ray in device memory) and write n rt_hit to
+ * dev_hits (device memory).  stream: a hipStream_t or NULL (the renderer's
+ * own); asynchronous unless stats != NULL, and ordered after the handle's
+ * earlier work, like rt_render.  With stats: primary_rays = n (nearest) or
+ * shadow_rays = n (any), nodes_visited / prims_tested summed over the rays,
+ * ms = device time of the launch.  n == 0: RT_OK, nothing launched.  No scene:
+ * RT_E_NOSCENE.  Unknown kind, or a NULL buffer with n > 0: RT_E_INVALID.
+ * Rays with a NaN or infinite component miss.  A query reads scene state only:
+ * it never changes a frame (progressive accumulation, counters, the next
+ * frame's image).  A multi-device handle answers from devices[0]. */
+int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kind, void* dev_hits,
+                  void* stream, rt_stats* stats);
+/* The nearest sphere under image coordinates (u, v) of the current camera
+ * (pixel (x, y)'s centre ray is u = x, v = y, as the frames cast it):
+ * Camera::getRay (include/camera.h:24-41) with tmin = 0, tmax = +inf.  Waits
+ * for the answer.  hit_out as above; point_out (may be NULL) = origin + t * dir.
+ * The Displayer's mouse position goes here. */
+int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]);
 
 /* ---- one process, several devices (SURVEY 8b B2 "device ids", 8e E1) ------ */
 /* A renderer handle that renders every frame across n_devices GPUs of this

@@ -145,6 +145,21 @@ public:
                               tile_size, dev_rgba8, stream),
               r_);
     }
+    // ray queries against the scene octree (rt_trace_rays): n rt_ray in device
+    // memory -> n rt_hit in device memory; kind RT_QUERY_NEAREST / RT_QUERY_ANY
+    void traceRays(const void* dev_rays, uint32_t n, void* dev_hits,
+                   uint32_t kind = RT_QUERY_NEAREST, void* stream = nullptr,
+                   rt_stats* stats = nullptr) {
+        check(rt_trace_rays(r_, dev_rays, n, kind, dev_hits, stream, stats), r_);
+    }
+    // the nearest sphere under image coordinates (u, v), e.g. the Displayer's
+    // mouse position (rt_pick); false on a miss.  point3: origin + t * dir, or null
+    bool pick(float u, float v, rt_hit* hit = nullptr, float* point3 = nullptr) {
+        rt_hit h;
+        check(rt_pick(r_, u, v, &h, point3), r_);
+        if (hit) *hit = h;
+        return h.sphere != RT_NO_HIT;
+    }
     rt_scene_info sceneInfo() const {
         rt_scene_info i;
         check(rt_get_scene_info(r_, &i), r_);

@@ -50,6 +50,9 @@ RT_TRANSPORT_AUTO = 0
 RT_TRANSPORT_RCCL = 1
 RT_TRANSPORT_PEER = 2
 RT_MAX_DEVICES = 16
+RT_NO_HIT = 0xFFFFFFFF    # rt_hit.sphere of a miss
+RT_QUERY_NEAREST = 0
+RT_QUERY_ANY = 1
 
 _f3 = ctypes.c_float * 3
 
@@ -159,6 +162,14 @@ class RtMultiTiming(ctypes.Structure):
                 "deliver_ms": round(float(self.deliver_ms), 4)}
 
 
+class RtRay(ctypes.Structure):
+    _fields_ = [("origin", _f3), ("tmin", ctypes.c_float), ("dir", _f3), ("tmax", ctypes.c_float)]
+
+
+class RtHit(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_float), ("sphere", ctypes.c_uint32)]
+
+
 class RtDisplayOps(ctypes.Structure):
     _fields_ = [("map", DISPLAY_MAP), ("unmap", DISPLAY_UNMAP)]
 
@@ -193,6 +204,8 @@ SIGNATURES = {
     "rt_bind_display": (_int, [_P, ctypes.POINTER(RtDisplayOps), _P]),
     "rt_render_tiles": (_int, [_P, _P, _u32, _u32, _P, _P, ctypes.POINTER(RtStats)]),
     "rt_unpack_tiles": (_int, [_P, _P, _P, _u32, _u32, _P, _P]),
+    "rt_trace_rays": (_int, [_P, _P, _u32, _u32, _P, _P, ctypes.POINTER(RtStats)]),
+    "rt_pick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),
     "rt_readback": (_int, [_P, _P, _P]),
@@ -216,7 +229,7 @@ test_flags = 0
 
 # the sources the scene kernel's machine code is built from (device code and
 # its compile flags): a PMC summary is valid for a build iff its stamp matches
-KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_params.h", "csrc/Makefile")
+KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_params.h", "csrc/Makefile")
 
 
 def kernel_source_id() -> str:

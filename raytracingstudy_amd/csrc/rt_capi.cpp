@@ -40,6 +40,9 @@ hipError_t launch_albedo_refs(const uint32_t* prim_idx, const uint32_t* albedo, 
                               uint32_t n_spheres, uint32_t* out, hipStream_t st);
 hipError_t launch_cam8_screen(const float4* prim_sp, uint32_t n, const float o[3], const float B[9],
                               uint32_t ok, float2* out, hipStream_t st);
+// rt_query.hip: n rays (rt_ray) -> n hits (rt_hit) against a.sc; counters != null: a stats launch
+hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32_t n, bool any,
+                        unsigned long long* counters, hipStream_t st);
 }  // namespace rtamd
 
 using namespace rtamd;
@@ -210,6 +213,11 @@ struct rt_renderer {
     // albedo by leaf reference (SceneArgs::prim_al) and the scene it was made for
     DevBuf<uint32_t> d_prim_al;
     uint64_t al_gen = ~0ull;
+    // ray queries (rt_trace_rays, rt_pick): their own stat lines (a query never
+    // touches the frames' counter sets) and rt_pick's one ray and one hit
+    DevBuf<unsigned long long> q_counters;
+    DevBuf<float4> q_ray;
+    DevBuf<uint2> q_hit;
     rt_scene_info info{};
     std::string err;
     // multi-device handle (rt_create_multi): this renderer is devices[0]'s
@@ -1223,6 +1231,9 @@ int rt_destroy(rt_renderer* r) {
     r->d_prim_shd8.release();
     r->d_shd_rr.release();
     r->d_prim_shd.release();
+    r->q_counters.release();
+    r->q_ray.release();
+    r->q_hit.release();
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();
@@ -1616,6 +1627,95 @@ int unpack_tiles_one(rt_renderer* r, const void* dev_packed, const uint32_t* til
 }  // namespace
 
 extern "C" {
+
+// Ray queries (the reference has none: Octree::traverse is a stub,
+// include/octree.h:19-21).  A query reads scene state only: it takes no frame
+// id, leaves the progressive sums, the frames' counter sets and the qerr word
+// alone, and is ordered after the handle's earlier work like every launch.
+int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kind, void* dev_hits,
+                  void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_trace_rays: null handle");
+    if (kind != RT_QUERY_NEAREST && kind != RT_QUERY_ANY)
+        return fail(r, RT_E_INVALID, "rt_trace_rays: unknown query kind");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_trace_rays: no scene (rt_set_scene first)");
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    if (!dev_rays || !dev_hits) return fail(r, RT_E_INVALID, "rt_trace_rays: null buffer");
+    int st;
+    if ((st = set_device(r))) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    // the kernel's leading argument is a FrameArgs (rt_query.hip): the scene, the rest zero
+    FrameArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sc = r->sc;
+    unsigned long long* ctr = nullptr;
+    constexpr size_t kLines = 8 * kStatLineStride;
+    if (stats) {
+        if ((st = ensure(r, r->q_counters, kLines))) return st;
+        ctr = r->q_counters.p;
+        RT_HIP(r, hipMemsetAsync(ctr, 0, kLines * sizeof(unsigned long long), hs));
+        RT_HIP(r, hipEventRecord(r->ev0, hs));
+    }
+    hipError_t e = launch_query(a, dev_rays, dev_hits, n, kind == RT_QUERY_ANY, ctr, hs);
+    if (e != hipSuccess) return hip_fail(r, e, "rt_trace_rays: kernel launch");
+    if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
+    if ((st = mark_queued(r, hs))) return st;
+    if (stats) {
+        RT_HIP(r, hipEventSynchronize(r->ev1));
+        unsigned long long lines[kLines], c[4] = {0, 0, 0, 0};
+        RT_HIP(r, hipMemcpy(lines, ctr, sizeof(lines), hipMemcpyDeviceToHost));
+        for (uint32_t q = 0; q < 8; ++q)
+            for (uint32_t i = 0; i < 4; ++i) c[i] += lines[q * kStatLineStride + i];
+        float ms = 0.f;
+        RT_HIP(r, hipEventElapsedTime(&ms, r->ev0, r->ev1));
+        memset(stats, 0, sizeof(*stats));
+        (kind == RT_QUERY_ANY ? stats->shadow_rays : stats->primary_rays) = n;
+        stats->nodes_visited = c[2];
+        stats->prims_tested = c[3];
+        stats->ms = ms;
+    }
+    return RT_OK;
+}
+
+int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]) {
+    if (!r || !hit_out) return fail(r, RT_E_INVALID, "rt_pick: null argument");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick: no scene (rt_set_scene first)");
+    // Camera::getRay (include/camera.h:24-41) in source order on the host (built
+    // with -ffp-contract=off, IEEE division and sqrt): the same bits as the CPU oracle's getRay
+    const float* K = r->K;
+    const float* P = r->pose;
+    const float dx = (u - K[2]) / K[0];
+    const float dy = (v - K[5]) / K[4];
+    const float dz = 1.0f;
+    float wx = P[0] * dx + P[4] * dy + P[8] * dz;
+    float wy = P[1] * dx + P[5] * dy + P[9] * dz;
+    float wz = P[2] * dx + P[6] * dy + P[10] * dz;
+    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
+    wx /= len;
+    wy /= len;
+    wz /= len;
+    const float4 ray[2] = {make_float4(P[12], P[13], P[14], 0.0f), make_float4(wx, wy, wz, INFINITY)};
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q_ray, 2)) || (st = ensure(r, r->q_hit, 1))) return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q_ray.p, ray, sizeof(ray), hipMemcpyHostToDevice, hs));
+    if ((st = rt_trace_rays(r, r->q_ray.p, 1, RT_QUERY_NEAREST, r->q_hit.p, hs, nullptr))) return st;
+    uint2 h;
+    RT_HIP(r, hipMemcpyAsync(&h, r->q_hit.p, sizeof(h), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    memcpy(&hit_out->t, &h.x, sizeof(float));
+    hit_out->sphere = h.y;
+    if (point_out) {
+        const float o[3] = {P[12], P[13], P[14]}, d[3] = {wx, wy, wz};
+        for (int i = 0; i < 3; ++i) point_out[i] = o[i] + hit_out->t * d[i];
+    }
+    return RT_OK;
+}
 
 int rt_reset_accumulation(rt_renderer* r) {
     if (!r) return fail(r, RT_E_INVALID, "rt_reset_accumulation: null handle");

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_params.h"
+#include "rt_walk.h"  // scene mode: the octree walk (shared with rt_query.hip)
 
 namespace rtamd {
 
@@ -128,756 +129,6 @@ __global__ void __launch_bounds__(kBlockThreads) compat_tiles_kernel(FrameArgs a
     const uint32_t y = (tile / a.tiles_x) * ts + ly;
     const uint32_t v = (x < a.W && y < a.H) ? compat_pixel(a.cam, x, y, a.contract) : 0u;
     a.out8[(size_t)k * ts * ts + ly * ts + lx] = v;
-}
-
-// ---------------------------------------------------------------------------
-// Scene mode
-// ---------------------------------------------------------------------------
-
-#ifdef RT_BLOCK_STATS
-// Diagnostic build: the first active lane counts one execution of block i by
-// the wave, and the active lanes (BlockStat, rt_params.h).
-__device__ __forceinline__ void bs_count(uint32_t* bs, uint32_t i) {
-    const uint64_t m = __ballot(1);
-    if (__lane_id() == static_cast<uint32_t>(__builtin_ctzll(m))) {
-        bs[2 * i] += 1u;
-        bs[2 * i + 1] += static_cast<uint32_t>(__popcll(m));
-    }
-}
-#define RT_BS(i) bs_count(bs, (i))
-#else
-#define RT_BS(i) ((void)0)
-#endif
-
-// Nearest root with the perpendicular-distance discriminant, explicit FMAs
-// (13 VALU to the h < 0 test); accepted iff tmin < t < tmax.  Same operations
-// as oracle.c:isect.  isect_oc takes o - c already formed (in the same f32
-// operations: the camera-relative records hold it), isect forms it.
-__device__ __forceinline__ bool isect_oc(float ocx, float ocy, float ocz, float d0, float d1,
-                                         float d2, float r, float tmin, float tmax, float& tout,
-                                         uint32_t* bs = nullptr) {
-    const float b = fmaf(ocz, d2, fmaf(ocy, d1, ocx * d0));
-    const float qx = fmaf(-b, d0, ocx);
-    const float qy = fmaf(-b, d1, ocy);
-    const float qz = fmaf(-b, d2, ocz);
-    const float qq = fmaf(qz, qz, fmaf(qy, qy, qx * qx));
-    const float h = fmaf(r, r, -qq);
-    if (h < 0.0f) return false;
-    RT_BS(kBsSqrt);
-    const float sq = sqrtf(h);
-    float t = -b - sq;
-    if (!(t > tmin)) t = -b + sq;
-    if (!(t > tmin) || !(t < tmax)) return false;
-    tout = t;
-    return true;
-}
-__device__ __forceinline__ bool isect(float o0, float o1, float o2, float d0, float d1, float d2,
-                                      float4 sp, float tmin, float tmax, float& tout,
-                                      uint32_t* bs = nullptr) {
-    const float ocx = o0 - sp.x;
-    const float ocy = o1 - sp.y;
-    const float ocz = o2 - sp.z;
-    return isect_oc(ocx, ocy, ocz, d0, d1, d2, sp.w, tmin, tmax, tout, bs);
-}
-
-// v_readlane of a float's bits (the builtin is int-typed: a float argument
-// would be converted to an integer value)
-__device__ __forceinline__ float readlane_f(float x, uint32_t lane) {
-    return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), lane));
-}
-
-// isect's discriminant h alone (same operations): h < 0 <=> isect rejects
-// the sphere before its square root.
-__device__ __forceinline__ float isect_h_oc(float ocx, float ocy, float ocz, float d0, float d1,
-                                            float d2, float r) {
-    const float b = fmaf(ocz, d2, fmaf(ocy, d1, ocx * d0));
-    const float qx = fmaf(-b, d0, ocx);
-    const float qy = fmaf(-b, d1, ocy);
-    const float qz = fmaf(-b, d2, ocz);
-    const float qq = fmaf(qz, qz, fmaf(qy, qy, qx * qx));
-    return fmaf(r, r, -qq);
-}
-__device__ __forceinline__ float isect_h(float o0, float o1, float o2, float d0, float d1,
-                                         float d2, float4 sp) {
-    const float ocx = o0 - sp.x;
-    const float ocy = o1 - sp.y;
-    const float ocz = o2 - sp.z;
-    return isect_h_oc(ocx, ocy, ocz, d0, d1, d2, sp.w);
-}
-
-// Camera-relative records (SceneArgs::prim_cam): 0 off; 1 =
-// {o - c, C'} with the slack screen fma(b, b, -C') >= 0 and the exact tests
-// reloading the chunk's spheres; 2 = {o - c, r}, the exact discriminant from
-// the stored o - c (isect's own operations, 10 VALU: no slack, no reload)
-#ifndef RT_CAM_MODE
-#define RT_CAM_MODE 1
-#endif
-constexpr int kCamMode = RT_CAM_MODE;
-
-// The kernel's FrameArgs as memory (the kernarg segment, scalar-cached),
-// behind an opaque pointer: a field read through it is a fresh s_load at that
-// point instead of a value kept live in an SGPR across the walk (the register
-// allocator would spill it into VGPR lanes: v_writelane / v_readlane, VALU
-// work per pixel).  Used for the per-sample camera, shading and output fields.
-typedef __attribute__((address_space(4))) const FrameArgs KernArgs;
-__device__ __forceinline__ KernArgs* kernargs() {
-    KernArgs* p = (KernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
-
-// An incomplete frame (FrameArgs::qerr): this frame's id into the renderer's
-// pinned host word, a plain system-scope store (no atomic over the host
-// link), visible to the host without a copy.  Called by a wave's lead lane.
-__device__ __forceinline__ void frame_failed() {
-    KernArgs* ka = kernargs();
-    __hip_atomic_store(ka->qerr, ka->frame_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-constexpr uint32_t kSortMaxRounds = 4;  // up to 256 samples per pixel
-constexpr uint32_t kSortMax = 64u * kSortMaxRounds;
-// per wave: per sample a slot {t, sphere} -> {lam | miss g, albedo | miss b}
-// and a kind byte; the tracing order and the list of lit samples (u8 each)
-constexpr uint32_t kSortCellBits = 3;  // jitter cells per axis: 2^3 (8 x 8, Morton order)
-constexpr uint32_t kSortCells = 1u << (2u * kSortCellBits);
-constexpr uint32_t kSortWaveBytes = kSortMax * 8u + 3u * kSortMax + kSortCells * 4u;
-static_assert(kSortWaveBytes % 16u == 0u, "per-wave regions stay float4-aligned");
-
-// rank of this lane among the lanes set in m
-__device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
-                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
-
-// LDS leaf staging (RT_LDS_LEAF): a per-wave buffer of
-// kLeafBuf spheres after the rest of the workgroup's LDS (pixel sums and
-// stacks, or the sorted path's stacks and per-wave regions).
-#ifndef RT_LDS_LEAF
-#define RT_LDS_LEAF 1
-#endif
-// Leaves of fewer spheres read them directly: staging adds an LDS round trip
-// to the first chunk, which a leaf of one or two chunks does not win back.
-// Measured (profiles/r05/ldsmin_ab.log, 3 alternating rounds, against no
-// staging): from 1 / 4 / 6 / 8 spheres C3 +1.0 / -0.7 / -1.7 / +0.2%, C5
-// -6.9 / -7.8 / -7.8 / -5.3%, C5d +4.0 / +2.5 / +2.3 / +2.5%.  Round 6, with
-// shadow walks no longer staging (kLdsShadow), against 6: from 2 / 3 / 4 / 5
-// spheres C3 +0.2 / -0.4 / -0.5 / -1.0%, C5 -0.8 / -1.1 / -1.2 / -1.3%, C5d
-// +1.0 / +0.5 / +0.3 / +0.1%, 8: C3 +3.5%, C5 +4.6%
-// (profiles/r06/ab_r6_lmin2_lmin3_lmin4_lmin5.log, ab_r6_lmin4_lmin8.log).
-#ifndef RT_LDS_MIN
-#define RT_LDS_MIN 5
-#endif
-constexpr uint32_t kLdsLeafMin = RT_LDS_MIN;
-// Only nearest-hit (primary) walks stage their leaves: a shadow ray may stop
-// at a leaf's first chunk, after a staging load fetched all of the leaf's
-// lines, and its chunked reads stop with it.  Against staging shadow leaves
-// too (RT_LDS_SHADOW=1, A/B): C5d -1.3%, C5 -0.5%, C3 -0.1%
-// (profiles/r06/ab_ctr3_noshst_sbo.log, 3 alternating rounds).
-#ifndef RT_LDS_SHADOW
-#define RT_LDS_SHADOW 0
-#endif
-constexpr bool kLdsShadow = RT_LDS_SHADOW != 0;
-// Shading by leaf reference (SceneArgs::prim_al): a nearest walk's `iout` is
-// the hit's reference, and shading reads prim_sp[ref] / prim_al[ref]; 0 keeps
-// the sphere index (prim_idx[ref]) and the by-index spheres / albedo arrays.
-// Measured (profiles/r06/ab_ref_shade.log, 3 alternating rounds): C3 -0.7%,
-// C5 -0.5%, C5d -0.2%, C2 0; L2 misses C3 -7.5%, C5d -11.5% (pmc_l2_*.json)
-#ifndef RT_REF_SHADE
-#define RT_REF_SHADE 1
-#endif
-// Light-plane records in 8 bytes (SceneArgs::prim_shd8): a shadow chunk's two
-// spheres in ONE dwordx4 (the texture path charges a load by instruction,
-// not by bytes: 16 cycles for a dwordx2 or a dwordx4), screened against the
-// scene's largest radius term.  C3 -2.0%, C5 -2.4%, C2 -2.8%, C5d -0.1%; the
-// looser radius sends 2% (C3, C5) to 6% (C5d) more shadow chunks down the
-// exact path (profiles/r06/ab_shd8.log, bstats_shd8.log).  0: 16-byte records
-#ifndef RT_SHD8
-#define RT_SHD8 1
-#endif
-// Image-plane screen for primary rays in 8 bytes (SceneArgs::prim_cam8,
-// DESIGN.md 5.1 round 6): the primary walks screen a chunk's two spheres
-// from ONE dwordx4 instead of two 16-byte camera-relative records, and stage
-// no leaves in LDS.  C3 -2.9%, C5 -2.4%, C5d -2.1%, C2 -1.9% (unsorted and
-// sorted walks, profiles/r06/ab_cam8_sorted.log); RT_CAM8=0: the 16-byte
-// camera-relative screen and its LDS staging
-#ifndef RT_CAM8
-#define RT_CAM8 1
-#endif
-// ... LDS staging of the 8-byte records, pairs per float4, from
-// kLdsLeafMin8 spheres: C3 +1.2 / +1.3 / +3.4% from 8 / 5 / 3 against none
-// (ab_cam8_staging.log), so off
-#ifndef RT_CAM8_LDS
-#define RT_CAM8_LDS 0
-#endif
-// ... for the sorted walks (C5, C5d) too
-#ifndef RT_CAM8_SORTED
-#define RT_CAM8_SORTED 1
-#endif
-#ifndef RT_CAM8_LDS_MIN
-#define RT_CAM8_LDS_MIN 5
-#endif
-constexpr uint32_t kLdsLeafMin8 = RT_CAM8_LDS_MIN;
-// ... each sphere's own rr' as bf16 in the records' low bytes (RT_SHD8_PER)
-// instead of the scene's largest
-#ifndef RT_SHD8_PER
-#define RT_SHD8_PER 0
-#endif
-// spheres per chunk of the shadow walks (with 8-byte records: two per dwordx4);
-// 4 spills 48-100 B and runs C3 +6%, C5 +8%, C5d +5% (profiles/r06/ab_shd_chunk4.log)
-#ifndef RT_SHD_CHUNK
-#define RT_SHD_CHUNK 2
-#endif
-constexpr size_t kLeafBufBytes = RT_LDS_LEAF ? (kBlockThreads / 64u) * kLeafBuf * sizeof(float4) : 0u;
-
-// Ancestor-stack levels per thread: depths 1..D-1, or K..D-1 with a cell table
-// (a pop above depth K jumps through the table instead).
-// Per-thread ancestor-stack levels.  Internal nodes sit at depths <
-// stack_depth (the deepest leaf), and with a cell table only depths >= K are
-// pushed: K .. stack_depth - 1 (C5: its tree stops at depth 8 under a
-// depth-12 grid, so 2 levels, not 6).  The stackless walk (kNoStack, sorted
-// pixels) keeps none when there is a table: an ancestor that is not the
-// current node re-enters through the table.
-__host__ __device__ inline uint32_t stack_levels(const SceneArgs& S, bool no_stack = false) {
-    if (no_stack && S.tab_k) return 0u;
-    const uint32_t sb = S.tab_k ? S.tab_k - 1u : 0u;
-    return S.stack_depth > 1u + sb ? S.stack_depth - 1u - sb : 1u;
-}
-
-// First float4 of this wave's LDS leaf buffer (the layout of scene_lds_bytes
-// and sort_lds_bytes).
-__device__ __forceinline__ uint32_t leaf_buf_base(const SceneArgs& S, bool sorted) {
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t head = sorted ? (stack_levels(S, true) * kBlockThreads * 8u +
-                                    (kBlockThreads / 64u) * kSortWaveBytes) / 16u
-                                 : kBlockThreads + stack_levels(S) * kBlockThreads / 2u;
-    return head + wave * kLeafBuf;
-}
-
-#ifndef RT_CAP_VALU
-#define RT_CAP_VALU 0
-#endif
-
-// LDS leaf staging by gfx950's direct global -> LDS load (RT_GLDS, VERDICT r05
-// item 5): ONE global_load_lds_dwordx4 writes spheres 0 .. cnt - 1 of the leaf
-// at src into dst[0 .. cnt - 1] without a VGPR round trip or a ds_write.  Its
-// LDS destination is M0 + 16 x lane id, so it needs cnt consecutive active
-// lanes: from the wave's first active lane l0, lane l0 + k fetches sphere k
-// into (dst - l0)[l0 + k].  Returns false (the caller stages through
-// registers) when lanes l0 .. l0 + cnt - 1 are not all active.  (Widening
-// exec to lanes 0 .. cnt - 1 inside an asm statement instead, the first
-// build, was wrong: the address temporary's VGPR then changes in lanes the
-// compiler keeps other lanes' loop-exit values in; plain frames differed.)
-// The explicit vmcnt(0) retires the DMA before the chunks' ds_reads (the
-// issuing wave is the reader: no barrier, MI355X_MICROARCH.md item 7).
-#ifndef RT_GLDS
-#define RT_GLDS 0
-#endif
-__device__ __forceinline__ bool glds_leaf(const float4* src, float4* dst, uint32_t cnt) {
-    typedef __attribute__((address_space(3))) void LdsV;
-    const uint64_t act = __ballot(1);
-    const uint32_t l0 = static_cast<uint32_t>(__builtin_ctzll(act));
-    const uint64_t run = ((1ull << cnt) - 1ull) << l0;  // cnt < kLeafBuf = 32
-    if (l0 + cnt > 64u || (act & run) != run) return false;
-    const uint32_t k = __lane_id() - l0;
-    if (k < cnt) __builtin_amdgcn_global_load_lds(src + k, (LdsV*)(dst - l0), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return true;
-}
-
-// Grid-space octree walk (DESIGN.md "Octree walk"): mirrored origin so every
-// direction component is >= 0 (the Revelles entry step of hit_sphere,
-// src/renderer.cu:23-43), cell planes at integer grid coordinates, descend by
-// mid-plane tests at the current t, leave a cell through its exit planes, and
-// pop to the common ancestor found from the highest flipped coordinate bit.
-// The per-thread ancestor stack lives in LDS, [depth-1][thread] (conflict-free).
-// kAnyHit: compile-time any-hit; with kDynAny the mode comes from `any_rt`
-// instead, so ONE inlined walk serves both the primary and the shadow ray.
-// kShadowL: this walk's any-hit rays are the frame's shadow rays, whose
-// direction is FrameArgs::L in every lane: only then may it use
-// the light-plane screen and keep its reciprocals wave-uniform.  Any other
-// any-hit walk (a per-lane direction: ambient occlusion, area lights) keeps
-// the full discriminant screen.
-template <bool kAnyHitT, int kChunk = 2, bool kDynAny = false, bool kStats = true,
-          bool kNoStack = false, bool kShadowL = false, bool kCam8 = false>
-__device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, float o2, float d0,
-                                     float d1, float d2, float tmin, float tmax, float& tout,
-                                     uint32_t& iout, uint32_t& n_nodes, uint32_t& n_prims,
-                                     uint2* __restrict__ stk, bool any_rt = false,
-                                     uint32_t* bs = nullptr, uint32_t lb_u = ~0u) {
-    static_assert(!kShadowL || kAnyHitT || kDynAny, "a shadow walk along L is an any-hit walk");
-    const bool kAnyHit = kDynAny ? any_rt : kAnyHitT;
-    const uint32_t D = S.max_depth;
-    const uint32_t G = 1u << D;
-    // Camera-relative screen: a nearest-hit walk is a primary
-    // ray, whose origin is the frame's camera origin, so its screen reads the
-    // per-frame records {o - c, C'} and tests fma(b, b, -C') >= 0 (4 VALU a
-    // sphere) instead of the full discriminant (13 VALU); the exact tests of a
-    // chunk that passes load the chunk's own sphere records (through a fresh
-    // kernel-argument read: no second array pointer lives in the walk).
-    // Shadow (any-hit) walks start at hit points and keep the full screen.
-    const bool cam = kCamMode != 0 && !kAnyHit;
-    const bool cam_exact = cam && kCamMode == 2;  // records {o - c, r}: the tests use them as they are
-    // 8-byte image-plane records (RT_CAM8, unsorted nearest walks): the
-    // lane's point s = (Bd).xy / (Bd).z, once per walk
-    const bool cam8 = kCam8 && cam && !cam_exact && kChunk % 2 == 0;
-    float s8x = 0.0f, s8y = 0.0f;
-    if (cam8) {
-        KernArgs* kb = kernargs();
-        const float px = fmaf(kb->cam8_B[2], d2, fmaf(kb->cam8_B[1], d1, kb->cam8_B[0] * d0));
-        const float py = fmaf(kb->cam8_B[5], d2, fmaf(kb->cam8_B[4], d1, kb->cam8_B[3] * d0));
-        const float pz = fmaf(kb->cam8_B[8], d2, fmaf(kb->cam8_B[7], d1, kb->cam8_B[6] * d0));
-        const float iz = __builtin_amdgcn_rcpf(pz);
-        s8x = px * iz;
-        s8y = py * iz;
-    }
-    // Light-plane screen: a shadow walk's direction is the
-    // frame's L in every lane, so a sphere is near the ray iff its centre is
-    // near the ray's origin in the plane perpendicular to L.  The records
-    // hold each centre's {u, v} there and a radius grown by the rounding
-    // bound, the lane its origin's {up, vp}: 5 VALU a sphere instead of 13.
-#ifdef RT_NO_SHADOW_SCREEN
-    constexpr bool kShdOk = false;
-#else
-    constexpr bool kShdOk = true;
-#endif
-    const bool shd = kShdOk && kShadowL && kAnyHit;  // a shadow ray along L (the caller says so)
-    float up = 0.0f, vp = 0.0f;
-    const bool shd8 = RT_SHD8 && kChunk % 2 == 0 && shd;
-    const float2* __restrict__ shd8_base = shd8 ? S.prim_shd8 : nullptr;
-    const float2* __restrict__ cam8_base = cam8 ? kernargs()->sc.prim_cam8 : nullptr;
-    const float shd_rr = shd8 ? kernargs()->shd_rr : 0.0f;
-    if (shd) {
-        KernArgs* ke = kernargs();
-        up = fmaf(o2, ke->shd_e[2], fmaf(o1, ke->shd_e[1], o0 * ke->shd_e[0]));
-        vp = fmaf(o2, ke->shd_e[5], fmaf(o1, ke->shd_e[4], o0 * ke->shd_e[3]));
-    }
-    const float4* __restrict__ prim_sp = cam ? S.prim_cam : shd ? S.prim_shd : S.prim_sp;
-    const uint2* __restrict__ nodes = S.nodes;
-    const float o[3] = {o0, o1, o2};
-    const float d[3] = {d0, d1, d2};
-    float inv[3], nog[3];
-    // Mirror mask packed in the cell table's index layout: field i (K bits,
-    // 1 without a table) is all ones iff axis i is mirrored, so a table
-    // index is the packed l >> (D - K) XOR mt (top - c == c ^ top for c <=
-    // top), and the descent's child mirror bits are each field's low bit.
-    const uint32_t kf = S.tab_k ? S.tab_k : 1u;
-    const uint32_t ftop = (1u << kf) - 1u;
-    uint32_t mt = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float g = (o[i] - S.rmin[i]) * S.scale[i];
-        const bool neg = d[i] < 0.0f;
-        float a = fabsf(d[i]);
-        if (a < 1e-20f) a = 1e-20f;
-        const float og = neg ? S.G - g : g;
-        inv[i] = 1.0f / (a * S.scale[i]);
-        // a shadow walk's direction is the frame's light direction, the same
-        // in every lane (sample_color_unified): its reciprocals live in SGPRs
-        if (kShadowL && kAnyHitT && !kDynAny)
-            inv[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(
-                                                   __builtin_bit_cast(uint32_t, inv[i])));
-        nog[i] = -(og * inv[i]);
-        mt |= neg ? ftop << (i * kf) : 0u;
-    }
-    // t of the grid plane at (mirrored) integer k: one FMA (oracle.c:plane)
-    auto plane = [&](int i, uint32_t k) { return fmaf(static_cast<float>(k), inv[i], nog[i]); };
-    float t0 = plane(0, 0), t1 = plane(0, G);
-#pragma unroll
-    for (int i = 1; i < 3; ++i) {
-        const float a0 = plane(i, 0), a1 = plane(i, G);
-        if (a0 > t0) t0 = a0;
-        if (a1 < t1) t1 = a1;
-    }
-    if (t0 < tmin) t0 = tmin;
-    if (t1 > tmax) t1 = tmax;
-    if (!(t0 < t1)) return false;
-    RT_BS(kBsWalk);
-
-    float best_t = tmax;
-    if (kStats) n_nodes += 1;
-
-    // Nearest keeps the best leaf *reference*; the sphere index is loaded only
-    // for an exact t tie (rare) and once at the end, so no dependent load sits
-    // in the hot loop.  Same result as the oracle's (min t, then min index).
-    uint32_t best_ref = kNoHit;
-    auto test = [&](const float4& sp, uint32_t ref) -> bool {
-        if (kStats) n_prims += 1;
-        RT_BS(kBsTest);
-        if (kAnyHit) RT_BS(kBsTestShadow);
-        float th;
-        if (cam_exact ? isect_oc(sp.x, sp.y, sp.z, d0, d1, d2, sp.w, tmin, tmax, th, bs)
-                      : isect(o0, o1, o2, d0, d1, d2, sp, tmin, tmax, th, bs)) {
-            RT_BS(kBsAccept);
-            if (kAnyHit) {
-                tout = th;
-                return true;
-            }
-            if (th < best_t) {
-                best_t = th;
-                best_ref = ref;
-            } else if (th == best_t) {
-                RT_BS(kBsTieLoad);
-                if (S.prim_idx[ref] < S.prim_idx[best_ref]) best_ref = ref;
-            }
-        }
-        return false;
-    };
-    // Leaf spheres in list order (same order, hence same counters, as the
-    // oracle): each lane loads its own, kChunk loads in flight.
-    // The chunk loop over one leaf's spheres (offset off, count cnt), each
-    // read as load(k), k counted from the leaf's first reference.
-    // plb: with 8-byte image-plane records staged in LDS (RT_CAM8_LDS), the
-    // wave's buffer, pairs of records per float4; ~0u: records from global
-    auto chunks = [&](auto&& load, uint32_t off, uint32_t cnt, uint32_t plb = ~0u) -> bool {
-        // cnt >= 1 (a leaf is a non-empty cell; the root leaf is guarded by
-        // its caller): a do-while skips the loop-entry test and its branch
-        uint32_t j = 0;
-        // Slot q of a chunk holds one of the leaf's spheres iff j + q < cnt.
-        // Slot 0 always does (j < cnt inside the do-while), and for q >= 1
-        // the test is j < cnt - q against a per-leaf bound: no per-chunk
-        // m = cnt - j, no second loop counter and no mask for slot 0.
-        const auto in_leaf = [&](int q) -> bool {
-            return q == 0 || static_cast<int>(j) < static_cast<int>(cnt) - q;
-        };
-        do {
-            RT_BS(kBsLeafChunk);
-            if (kAnyHit) RT_BS(kBsChunkShadow);
-            // kChunk unconditional dwordx4 loads in flight at fixed offsets; a
-            // slot past the leaf's end reads the next leaf or the array's
-            // kPrimPad tail (in bounds) and is never tested
-            float4 sv[kChunk];
-            // slot q >= 1 is fetched only when some lane's leaf still holds
-            // it (RT_SKIP_PAST_END, a wave-uniform branch): a wave-wide load
-            // costs the texture path as much for one lane as for 64, and at
-            // a leaf's odd end the whole wave usually has no slot 1
-            bool fetched[kChunk];
-            if (shd8 || cam8) {
-                // two slots' 8-byte records per dwordx4 (8-byte aligned:
-                // global loads need dword alignment only; an even kChunk)
-#pragma unroll
-                for (int h = 0; h < kChunk / 2; ++h) {
-                    extern __shared__ __attribute__((aligned(16))) float4 lds_pairs[];
-                    const float4 pr = cam8 && plb != ~0u
-                                          ? lds_pairs[plb + (j >> 1) + h]
-                                          : *reinterpret_cast<const float4*>((cam8 ? cam8_base : shd8_base) +
-                                                                             (off + j + 2u * h));
-                    sv[2 * h] = make_float4(pr.x, pr.y, 0.0f, 0.0f);
-                    sv[2 * h + 1] = make_float4(pr.z, pr.w, 0.0f, 0.0f);
-                    fetched[2 * h] = fetched[2 * h + 1] = true;
-                }
-            } else
-#pragma unroll
-            for (int q = 0; q < kChunk; ++q) {
-#ifdef RT_SKIP_PAST_END
-                fetched[q] = q == 0 || __any(in_leaf(q));
-                if (fetched[q]) sv[q] = load(j + q);
-                else sv[q] = sv[0];
-#else
-                fetched[q] = true;
-                sv[q] = load(j + q);
-#endif
-                // issue in list order, so the first test waits for its own
-                // sphere only (vmcnt(kChunk-1)), not for the whole chunk
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // Uniform screen: every lane's discriminants first, with no branch;
-            // only when some lane's h is >= 0 (or NaN) does the wave run the
-            // exact per-lane tests (which recompute them), one branch for the
-            // chunk instead of a divergent branch per test.  h < 0 is exactly
-            // where isect returns false, so the same spheres are accepted.
-            bool maybe = false;
-#pragma unroll
-            for (int q = 0; q < kChunk; ++q) {
-                // unconditional and unmasked: a slot past the leaf's end holds
-                // a real sphere record too, and if it passes the screen the
-                // exact tests below still skip it (in_leaf), so it can only
-                // send the chunk down the exact path for nothing
-                bool pos;
-                if (cam_exact) {
-                    pos = !(isect_h_oc(sv[q].x, sv[q].y, sv[q].z, d0, d1, d2, sv[q].w) < 0.0f);
-                } else if (cam8) {
-                    // the lane's image-plane distance from the centre's
-                    // projection against rho^2 (bf16 in the records' low bytes)
-                    const float rho2 = __uint_as_float(__builtin_amdgcn_perm(
-                        __float_as_uint(sv[q].x), __float_as_uint(sv[q].y), 0x04000C0Cu));
-                    const float dx = s8x - sv[q].x, dy = s8y - sv[q].y;
-                    pos = !(fmaf(dy, dy, dx * dx) > rho2);
-                } else if (cam) {
-                    // b exactly as isect computes it ({x,y,z} = o - c in the
-                    // same f32 operations); C' undercuts |o-c|^2 - r^2 by the
-                    // rounding bound, so every sphere isect accepts passes
-                    const float b = fmaf(sv[q].z, d2, fmaf(sv[q].y, d1, sv[q].x * d0));
-                    pos = !(fmaf(b, b, -sv[q].w) < 0.0f);
-                } else if (shd) {
-                    // the centre's light-plane distance from the origin; rr'
-                    // covers the rounding, so every sphere isect accepts passes
-                    const float du = up - sv[q].x, dv = vp - sv[q].y;
-                    const float rr8 = RT_SHD8_PER ? __uint_as_float(__builtin_amdgcn_perm(
-                                                         __float_as_uint(sv[q].x), __float_as_uint(sv[q].y),
-                                                         0x04000C0Cu))
-                                                   : shd_rr;
-                    pos = !(fmaf(dv, dv, du * du) > (shd8 ? rr8 : sv[q].z));
-                } else {
-                    pos = !(isect_h(o0, o1, o2, d0, d1, d2, sv[q]) < 0.0f);
-                }
-                maybe |= fetched[q] && pos;
-            }
-            // marked unlikely (it is: most chunks pass no lane): the exact
-            // tests are laid out off the fall-through path (C3 -0.6%, C5
-            // -0.7%, profiles/r02/branch_hint_ab.log)
-#ifdef RT_BLOCK_STATS
-            if (j + 1u >= cnt) RT_BS(kBsPastEnd);
-#endif
-            if (__builtin_expect(__any(maybe), 0)) {
-                if ((cam && !cam_exact) || shd) {  // the exact tests need the spheres themselves (cam8 too)
-                    RT_BS(kBsExactLoad);
-                    const float4* __restrict__ ex = kernargs()->sc.prim_sp + off;
-#pragma unroll
-                    for (int q = 0; q < kChunk; ++q) sv[q] = ex[j + q];
-                }
-#pragma unroll
-                for (int q = 0; q < kChunk; ++q)
-                    if (in_leaf(q) && test(sv[q], off + j + q)) return true;
-            } else if (kStats) {
-                n_prims += min(cnt - j, static_cast<uint32_t>(kChunk));
-            }
-            j += kChunk;
-        } while (j < cnt);
-        return false;
-    };
-    auto leaf = [&](uint32_t off, uint32_t cnt) -> bool {
-        static_assert(kChunk <= kPrimPad + 1, "leaf loads may run kChunk-1 spheres past a leaf");
-        RT_BS(kBsLeaf);
-#if RT_LDS_LEAF
-        // A leaf the whole wave is at (the common case: one pixel's samples
-        // walk together): its spheres cross the texture path ONCE, each
-        // active lane fetching one into the wave's LDS leaf buffer, and the
-        // chunks read them back by LDS broadcast (every lane the same
-        // address): one dwordx4 texture instruction per leaf visit instead
-        // of two per chunk (DESIGN.md 5.1 "LDS leaf staging").  The buffer
-        // is a typed LDS array, never a generic pointer (round 3's flat
-        // loads).  A slot past the leaf's end holds a stale sphere, which
-        // the exact tests skip as before.
-        const uint32_t off_u = __builtin_amdgcn_readfirstlane(off);
-        const uint32_t cnt_u = __builtin_amdgcn_readfirstlane(cnt);
-        if ((kLdsShadow || !kAnyHit) && !cam8 && cnt_u >= kLdsLeafMin && cnt_u < kernargs()->sc.lds_max &&
-            __all(off == off_u)) {
-            RT_BS(kBsLdsLeaf);
-            extern __shared__ __attribute__((aligned(16))) float4 lds_leaf[];
-            // (lb_u: the caller's wave-uniform copy, an SGPR; else from threadIdx)
-            const uint32_t lb = lb_u != ~0u ? lb_u : leaf_buf_base(S, kNoStack);
-            const float4* __restrict__ pu = prim_sp + off_u;
-            if (!RT_GLDS || !glds_leaf(pu, lds_leaf + lb, cnt_u)) {
-                const uint64_t act = __ballot(1);
-                const uint32_t na = static_cast<uint32_t>(__popcll(act));
-                for (uint32_t k = lane_rank(act); k < cnt_u; k += na) lds_leaf[lb + k] = pu[k];
-            }
-            // (a wave's LDS operations complete in order: the reads below see
-            // the writes, and the compiler keeps them in order: same array)
-            return chunks([&](uint32_t k) { return lds_leaf[lb + k]; }, off_u, cnt_u);
-        }
-        // the same for 8-byte image-plane records: pairs of records, one
-        // float4 per active lane, the chunks reading a pair per ds_read_b128
-        if (RT_CAM8_LDS && cam8 && cnt_u >= kLdsLeafMin8 && cnt_u < 2u * kernargs()->sc.lds_max &&
-            __all(off == off_u)) {
-            RT_BS(kBsLdsLeaf);
-            extern __shared__ __attribute__((aligned(16))) float4 lds_leaf[];
-            const uint32_t lb = lb_u != ~0u ? lb_u : leaf_buf_base(S, kNoStack);
-            const float4* __restrict__ pu = reinterpret_cast<const float4*>(cam8_base + off_u);
-            const uint32_t np = (cnt_u + 1u) >> 1;  // pairs (an odd leaf's last pair reads one past it)
-            const uint64_t act = __ballot(1);
-            const uint32_t na = static_cast<uint32_t>(__popcll(act));
-            for (uint32_t k = lane_rank(act); k < np; k += na) lds_leaf[lb + k] = pu[k];
-            return chunks([&](uint32_t k) { return lds_leaf[lb + k]; }, off_u, cnt_u, lb);
-        }
-#endif
-        const float4* __restrict__ ps = prim_sp + off;
-        return chunks([&](uint32_t k) { return ps[k]; }, off, cnt);
-    };
-
-    if (S.root_is_leaf) {
-        if (S.root.y && leaf(S.root.x, S.root.y)) return true;  // an empty scene's root holds 0
-    } else {
-        uint2 node = S.root;
-        // Cell = (depth, lower corner l* in finest-grid units, size = G >> depth):
-        // mid plane = l + size/2, exit plane = l + size: the same integers (hence
-        // the same plane values) as the oracle's c * size forms, 3 VALU a plane.
-        uint32_t depth = 0, l0 = 0, l1 = 0, l2 = 0, size = G;
-        float t = t0;
-        // Cell table: the walk enters at depth K through one
-        // table load, and a step whose common ancestor lies above depth K
-        // jumps the same way instead of re-reading the records down to K.
-        const uint2* __restrict__ tab = S.tab;
-        const uint32_t K = S.tab_k;
-        bool jump = tab != nullptr;
-        uint32_t from = 0;  // depth the oracle re-descends from (stats)
-        // with a table, only depths >= K are ever on the stack (stack_levels);
-        // the stackless walk (kNoStack) keeps one only without a table
-        const uint32_t sb = K ? K - 1u : 0u;
-        // Hard cap (never reached by a correct walk: a ray crosses < 3*G cells
-        // and each crossing costs at most one descent): no input can hang the GPU.
-        // One exit per trip (`stop`): the any-hit, nearest-done, ray-left and
-        // root-left conditions are OR-ed into one flag, so the wave's exec
-        // bookkeeping is one loop-exit mask update per trip (the scalar pipe is
-        // this kernel's busiest unit, profiles/r02/pmc_sq_screen.json).
-        bool any_hit = false;
-#if RT_CAP_VALU
-        // the trip counter as a lane value (an opaque v_mov): the cap test is
-        // one VALU compare feeding the exit mask, not SALU add / compare /
-        // select on the scalar pipe (A/B)
-        uint32_t it;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(it));
-        for (const uint32_t cap = 8u * G + 64u;; ++it) {
-#else
-        for (uint32_t it = 0, cap = 8u * G + 64u;; ++it) {
-#endif
-            RT_BS(kBsIter);
-            if (kAnyHit) RT_BS(kBsIterShadow);
-            uint2 rec = make_uint2(0u, 0u);
-            bool have = false;   // rec is a leaf record (else the cell is empty)
-            bool inner = false;  // stepped into an internal node: descend next trip
-            if (jump) {
-                RT_BS(kBsJump);
-                jump = false;
-                // mid-plane tests at t from `depth` down to K (no loads: the
-                // descent's child choices), then the cell's table entry
-                while (depth < K) {
-                    RT_BS(kBsJumpDescend);
-                    if (kAnyHit) RT_BS(kBsJumpDescendShadow);
-                    const uint32_t half = size >> 1;
-                    l0 += plane(0, l0 + half) <= t ? half : 0u;
-                    l1 += plane(1, l1 + half) <= t ? half : 0u;
-                    l2 += plane(2, l2 + half) <= t ? half : 0u;
-                    size = half;
-                    depth += 1;
-                }
-                const uint32_t sh = D - K;
-                // real cell coordinates: mirrored axes count from the far side
-                // (the XOR with mt flips every mirrored field at once)
-                const uint32_t c = ((((l2 >> sh) << K) | (l1 >> sh)) << K | (l0 >> sh)) ^ mt;
-                const uint2 e = tab[c];
-                const uint32_t kind = e.y >> kCellKindShift;
-                depth = (e.y >> kCellDepthShift) & 31u;
-                size = G >> depth;
-                l0 &= ~(size - 1u);
-                l1 &= ~(size - 1u);
-                l2 &= ~(size - 1u);
-                rec = make_uint2(e.x, e.y & kCellRecMask);
-                // the oracle reads one record per level from `from` down to
-                // the covering node (an empty child's own level reads none)
-                // (a re-entry below K re-reads levels the oracle pops: none counted)
-                if (kStats) {
-                    const uint32_t cd = kind == kCellEmpty ? depth - 1u : depth;
-                    n_nodes += cd > from ? cd - from : 0u;
-                }
-                inner = kind == kCellInternal;
-                have = kind == kCellLeaf;
-            } else {
-                RT_BS(kBsDescend);
-                const uint32_t half = size >> 1;
-                const bool b0 = plane(0, l0 + half) <= t;
-                const bool b1 = plane(1, l1 + half) <= t;
-                const bool b2 = plane(2, l2 + half) <= t;
-                const uint32_t bits = (b0 ? 1u : 0u) | (b1 ? 2u : 0u) | (b2 ? 4u : 0u);
-                const uint32_t mbits = (mt & 1u) | ((mt >> (kf - 1u)) & 2u) |
-                                       ((mt >> (2u * kf - 2u)) & 4u);
-                const uint32_t child = bits ^ mbits;
-                l0 += b0 ? half : 0u;
-                l1 += b1 ? half : 0u;
-                l2 += b2 ? half : 0u;
-                size = half;
-                depth += 1;
-                const uint32_t valid = node.y & 0xFFu;
-                have = (valid & (1u << child)) != 0;
-                if (have) {
-                    const uint32_t slot = node.x + __builtin_popcount(valid & ((1u << child) - 1u));
-                    rec = nodes[slot];
-#ifdef RT_BLOCK_STATS
-                    if (depth > from) RT_BS(kBsNodeRead);
-                    else RT_BS(kBsNodeReread);
-#endif
-                    // records down to a re-entered ancestor are the oracle's
-                    // stack pops, not reads
-                    if (kStats && depth > from) n_nodes += 1;
-                    inner = !((node.y >> 8) & (1u << child));
-                    have = !inner;
-                }
-            }
-            // An internal node: descend next trip.  No `continue` and no break
-            // inside the step: the rest of the trip is the else branch, and the
-            // loop's one exit is `stop` at the end of the trip (a stopped lane's
-            // step state is garbage it never uses; its pop is masked off), so
-            // the structurizer keeps no exit-code variable: C3 -3.3%, C5 -3.3%,
-            // C5d -3.8% (profiles/r02/inner_else_ab.log).
-            bool stop = false;
-            if (inner) {
-                RT_BS(kBsInternal);
-                node = rec;
-                if (!kNoStack || !tab) stk[(depth - 1 - sb) * kBlockThreads] = rec;
-            } else {
-                if (have) any_hit = leaf(rec.x, rec.y);
-                RT_BS(kBsExit);
-                const float e0 = plane(0, l0 + size);
-                const float e1 = plane(1, l1 + size);
-                const float e2 = plane(2, l2 + size);
-                // one v_min3_f32 (the oracle's ternaries can differ only in the sign
-                // of a zero, and texit is only ever compared: identical walks)
-                const float texit = fminf(fminf(e0, e1), e2);
-                // step every axis whose exit plane is texit; the flipped bits give the
-                // common ancestor (oracle.c: diff of the cell coordinates)
-                const uint32_t n0 = e0 == texit ? l0 + size : l0;
-                const uint32_t n1 = e1 == texit ? l1 + size : l1;
-                const uint32_t n2 = e2 == texit ? l2 + size : l2;
-                // leave on an any-hit, a nearest hit before this cell's exit, or
-                // the ray's end.  The oracle's root-boundary test (a stepped
-                // coordinate reaching G) needs no term of its own: an axis that
-                // steps to G exits through plane(i, G), the very value t1 is
-                // the minimum of, so texit >= t1 already holds there.
-                stop = any_hit | (!kAnyHit & (best_t < texit)) | (texit >= t1);
-                const uint32_t diff = (l0 ^ n0) | (l1 ^ n1) | (l2 ^ n2);
-                const uint32_t top = 31u - __builtin_clz(diff);  // highest flipped bit
-                t = texit;
-                // The common ancestor: size 2^(top+1), depth D - (top+1).  With a
-                // table the walk re-enters through it unless the ancestor is the
-                // node it iterates (m == 1): above depth K, or (no ancestor stack)
-                // two or more levels up.  A cell at depth >= K indexes the table
-                // straight from the neighbour's corner (`keep`) and re-descends
-                // by records; a shallower one resolves down to K from the
-                // ancestor's cell.  Without a table it pops to the ancestor.
-                // Selects, not branches: every lane ends the trip with the same
-                // instructions (the scalar pipe carries the branches' exec-mask
-                // updates, and it is the kernel's busiest unit).
-                const uint32_t adepth = D - (top + 1u);
-                const uint32_t m = depth - adepth;  // levels up to the ancestor
-                const bool above = adepth < K || (kNoStack && K != 0u && m > 1u);
-                const bool keep = above && depth >= K;
-                const uint32_t asize = 2u << top;
-                const uint32_t am = keep ? 0xFFFFFFFFu : ~(asize - 1u);
-                l0 = n0 & am;
-                l1 = n1 & am;
-                l2 = n2 & am;
-                size = keep ? size : asize;
-                depth = keep ? depth : adepth;
-                if (kStats && above) from = adepth;
-                jump = above;
-                // m == 1: the ancestor is the node we are iterating (still in `node`)
-                if (!stop && !above && m > 1) {  // (the stackless walk: only without a table)
-                    RT_BS(kBsPop);
-                    node = depth ? stk[(depth - 1 - sb) * kBlockThreads] : S.root;
-                }
-            }
-            // the safety cap shares the one exit (C3 -0.3%, profiles/r02/cap_exit_ab.log)
-            if (stop || it + 1u >= cap) break;
-        }
-        if (any_hit) return true;
-    }
-    if (!kAnyHit && best_ref != kNoHit) {
-        if (!RT_REF_SHADE) RT_BS(kBsHitIdx);
-        tout = best_t;
-        iout = RT_REF_SHADE ? best_ref : S.prim_idx[best_ref];
-        return true;
-    }
-    return false;
 }
 
 // ---------------------------------------------------------------------------

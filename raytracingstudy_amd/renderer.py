@@ -37,6 +37,7 @@ __all__ = ["KernelRenderer", "resize_intrinsic", "generate_spheres", "device_cou
            "save_spheres", "load_spheres"]
 
 _MODES = {"compat": RT_MODE_COMPAT, "scene": RT_MODE_SCENE}
+_QUERY_KINDS = {"nearest": _lib.RT_QUERY_NEAREST, "any": _lib.RT_QUERY_ANY}
 
 
 def _fptr(a: np.ndarray):
@@ -316,6 +317,52 @@ class KernelRenderer:
                                         ids.shape[0], int(tile_size),
                                         ctypes.c_void_p(dev_rgba8) if dev_rgba8 else None,
                                         ctypes.c_void_p(stream) if stream else None), self._h)
+
+    # -- ray queries (rt_trace_rays / rt_pick) -----------------------------------
+    def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, kind: str = "nearest",
+                          stream: Optional[int] = None, stats: bool = False) -> Optional[RtStats]:
+        """rt_trace_rays on buffers already on the GPU: n rt_ray (32 bytes each:
+        origin, tmin, dir, tmax) at rays_ptr -> n rt_hit (t, sphere) at hits_ptr.
+        Asynchronous on `stream` (None: the renderer's own) unless stats."""
+        st = RtStats() if stats else None
+        check(self._lib.rt_trace_rays(self._h, ctypes.c_void_p(rays_ptr) if rays_ptr else None,
+                                      int(n), _QUERY_KINDS[kind],
+                                      ctypes.c_void_p(hits_ptr) if hits_ptr else None,
+                                      ctypes.c_void_p(stream) if stream else None,
+                                      ctypes.byref(st) if st is not None else None), self._h)
+        return st
+
+    def trace_rays(self, rays, kind: str = "nearest", stats: bool = False):
+        """Trace a host (n, 8) float32 array of rays in rt_ray layout (origin xyz,
+        tmin, dir xyz, tmax): uploads, runs rt_trace_rays, and returns
+        (t (n,) float32, sphere (n,) uint32[, RtStats]).  A miss has t = the
+        ray's tmax and sphere = RT_NO_HIT."""
+        import torch
+        ra = np.ascontiguousarray(rays, np.float32)
+        if ra.ndim != 2 or ra.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) float32 array in rt_ray layout")
+        if not ra.flags.writeable:  # torch.from_numpy wants a writable array
+            ra = ra.copy()
+        n = ra.shape[0]
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_rays = torch.from_numpy(ra).to(dev)
+        d_hits = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
+        st = self.trace_rays_device(d_rays.data_ptr() if n else 0, n, d_hits.data_ptr() if n else 0,
+                                    kind, None, stats)
+        self.synchronize()
+        hits = d_hits[:n].cpu().numpy()
+        t = np.ascontiguousarray(hits[:, 0]).view(np.float32)
+        sphere = np.ascontiguousarray(hits[:, 1]).view(np.uint32)
+        return (t, sphere, st) if stats else (t, sphere)
+
+    def pick(self, u: float, v: float):
+        """rt_pick: the nearest sphere under image coordinates (u, v) of the current
+        camera -> (hit: bool, t, sphere, point (3,) float32)."""
+        h = _lib.RtHit()
+        pt = np.zeros(3, np.float32)
+        check(self._lib.rt_pick(self._h, float(u), float(v), ctypes.byref(h), _fptr(pt)), self._h)
+        return h.sphere != _lib.RT_NO_HIT, float(h.t), int(h.sphere), pt
 
     def reset_accumulation(self) -> None:
         """Progressive mode: the next frame starts from zero samples."""

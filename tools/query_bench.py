@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Ray-query throughput (rt_trace_rays) on a config's scene, coherent and incoherent rays.
+
+    python tools/query_bench.py [--config c3] [--log2-rays 22] [--reps 20] [--warmup 3]
+
+Two ray sets of 2^k rays each, nearest and any-hit, timed with HIP events around
+the launch on a stream (median of --reps launches after --warmup):
+  coherent    the config's own frame: pixel-centre camera rays in row-major
+              order (repeated from the first pixel when the frame has fewer)
+  incoherent  origins just off random spheres' surfaces, uniformly random
+              directions (neighbouring lanes share nothing)
+Prints one JSON line: Mrays/s, hit fraction and the walk's work per ray (from
+one stats launch) for each set and kind.  Needs a GPU: there is no fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import raytracingstudy_amd as rt  # noqa: E402
+from raytracingstudy_amd.camera import scene_pose  # noqa: E402
+
+
+def camera_rays(n: int, w: int, h: int, pose: np.ndarray, K: np.ndarray) -> np.ndarray:
+    """Camera::getRay (include/camera.h:24-41) at pixel centres, row-major, f32."""
+    f = np.float32
+    i = np.arange(n, dtype=np.int64) % (w * h)
+    u, v = (i % w).astype(f), (i // w).astype(f)
+    dx, dy = (u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1]
+    d = np.stack([pose[0, c] * dx + pose[1, c] * dy + pose[2, c] for c in range(3)], 1).astype(f)
+    d /= np.sqrt((d * d).sum(1, dtype=f))[:, None]
+    rays = np.zeros((n, 8), f)
+    rays[:, :3] = pose[3, :3]
+    rays[:, 4:7] = d
+    rays[:, 7] = np.inf
+    return rays
+
+
+def surface_rays(n: int, sp: np.ndarray, seed: int) -> np.ndarray:
+    g = np.random.default_rng(seed)
+
+    def unit(m):
+        x = g.normal(size=(m, 3))
+        return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+    k = g.integers(0, len(sp), n)
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, :3] = sp[k, :3] + np.float32(1.001) * sp[k, 3:4] * unit(n)
+    rays[:, 3] = 1e-5
+    rays[:, 4:7] = unit(n)
+    rays[:, 7] = np.inf
+    return rays
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="c3")
+    ap.add_argument("--log2-rays", type=int, default=22)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    if rt.device_count() == 0:
+        sys.exit("query_bench: no HIP device visible (rates are measured on the GPU only)")
+    cfg = rt.CONFIGS[args.config]
+    n = 1 << args.log2_rays
+    sp, al = rt.configs.scene_spheres(cfg, rt.SEED)
+    r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=cfg.spp)
+    r.resize(cfg.width, cfg.height)
+    pose = scene_pose()
+    r.setPosition(pose)
+    info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    _, K = r.camera()
+    sets = {"coherent": camera_rays(n, cfg.width, cfg.height, pose, K),
+            "incoherent": surface_rays(n, sp, 12345)}
+    stream = torch.cuda.Stream()
+    d_hits = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+    out = {"config": args.config, "rays": n, "reps": args.reps, "warmup": args.warmup,
+           "scene": {k: info[k] for k in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
+                                          "cell_table_depth")}}
+    for name, rays in sets.items():
+        d_rays = torch.from_numpy(rays).cuda()
+        torch.cuda.synchronize()
+        for kind in ("nearest", "any"):
+            def launch():
+                r.trace_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), kind,
+                                    stream=stream.cuda_stream)
+            for _ in range(args.warmup):
+                launch()
+            ms = []
+            for _ in range(args.reps):
+                e0 = torch.cuda.Event(enable_timing=True)
+                e1 = torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                launch()
+                e1.record(stream)
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            st = r.trace_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), kind,
+                                     stream=stream.cuda_stream, stats=True)
+            hit = float((d_hits[:, 1] != -1).float().mean().item())
+            med = float(np.median(ms))
+            out[f"{name}_{kind}"] = {
+                "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                "Mrays_s": round(n / med / 1e3, 1), "hit_fraction": round(hit, 4),
+                "nodes_per_ray": round(st.nodes_visited / n, 3),
+                "prims_per_ray": round(st.prims_tested / n, 3),
+                "stats_launch_ms": round(float(st.ms), 4)}
+    print(json.dumps(out))
+    r.close()
+
+
+if __name__ == "__main__":
+    main()
