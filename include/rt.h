@@ -36,6 +36,8 @@
  *     include/octree.h:19-21; no ray entry point)
  *   (none: Octree::traverse is a stub; the Displayer's    rt_pick
  *     mouse input selects nothing)
+ *   (none: one colour per pixel,                          rt_render_gbuffer
+ *     src/renderer.cu:57-82)
  *   (none: no error reporting, all void)                  rt_last_error
  *
  * Threading: one handle per host thread / stream; calls on one handle are not
@@ -346,6 +348,38 @@ int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kin
  * for the answer.  hit_out as above; point_out (may be NULL) = origin + t * dir.
  * The Displayer's mouse position goes here. */
 int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]);
+
+/* ---- first-hit G-buffer --------------------------------------------------- */
+/* The per-pixel geometry of the frame the current size and camera would
+ * render: an id buffer (hover highlight, rubber-band selection), a depth
+ * buffer (compositing rastered gizmos against the traced scene), normal and
+ * albedo guide layers (a denoiser at low sample counts).  The reference has no
+ * counterpart (its kernel writes one colour per pixel, src/renderer.cu:57-82).
+ * Pixel (x, y)'s ray is rt_pick(x, y)'s and the frames' unjittered sample's:
+ * origin pose[3].xyz, direction Camera::getRay(x, y) in source order (never the
+ * RT_FLAG_COMPAT_FMA candidate), tmin = 0, tmax = +inf, nearest hit.
+ * Three caller-owned device buffers in frame layout (row-major, pixel y*W + x),
+ * each optional (NULL: not written); every pixel of a given buffer is written:
+ *   dev_hits     rt_hit    {t, sphere} as rt_pick(x, y);   miss {+inf, RT_NO_HIT}
+ *   dev_normals  float[4]  n = (o + t*d - c) * (1.0f / r), the frames' shading
+ *                          normal, w = 0;                   miss four zeros
+ *   dev_albedo   uint32    the sphere's packed RGBA8 as the frames shade it
+ *                          (0xFFCCCCCC without albedo);     miss 0
+ * A camera inside a sphere reports the far root, like the frames. */
+typedef struct rt_gbuffer {
+    void* dev_hits;    /* W*H rt_hit, or NULL   */
+    void* dev_normals; /* W*H float[4], or NULL */
+    void* dev_albedo;  /* W*H uint32, or NULL   */
+} rt_gbuffer;
+/* stream: a hipStream_t or NULL (the renderer's own); asynchronous unless
+ * stats != NULL, and ordered after the handle's earlier work, like
+ * rt_trace_rays.  With stats: primary_rays = W*H, nodes_visited / prims_tested
+ * summed over the pixels, ms = device time of the launch, the rest 0.  NULL
+ * `out` or all three buffers NULL: RT_E_INVALID.  No scene: RT_E_NOSCENE.
+ * Reads scene and camera state only: it never changes a frame (progressive
+ * accumulation, counters, the framebuffer, the next frame's image).  A
+ * multi-device handle answers from devices[0] with the whole frame. */
+int rt_render_gbuffer(rt_renderer* r, const rt_gbuffer* out, void* stream, rt_stats* stats);
 
 /* ---- one process, several devices (SURVEY 8b B2 "device ids", 8e E1) ------ */
 /* A renderer handle that renders every frame across n_devices GPUs of this

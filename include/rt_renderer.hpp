@@ -160,6 +160,13 @@ public:
         if (hit) *hit = h;
         return h.sphere != RT_NO_HIT;
     }
+    // first-hit G-buffer of the current camera (rt_render_gbuffer): W*H rt_hit,
+    // float[4] normals and packed RGBA8 albedo in device memory, each optional
+    void renderGBuffer(void* dev_hits, void* dev_normals = nullptr, void* dev_albedo = nullptr,
+                       void* stream = nullptr, rt_stats* stats = nullptr) {
+        const rt_gbuffer g{dev_hits, dev_normals, dev_albedo};
+        check(rt_render_gbuffer(r_, &g, stream, stats), r_);
+    }
     rt_scene_info sceneInfo() const {
         rt_scene_info i;
         check(rt_get_scene_info(r_, &i), r_);

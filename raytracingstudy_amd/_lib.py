@@ -170,6 +170,11 @@ class RtHit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("sphere", ctypes.c_uint32)]
 
 
+class RtGBuffer(ctypes.Structure):
+    _fields_ = [("dev_hits", ctypes.c_void_p), ("dev_normals", ctypes.c_void_p),
+                ("dev_albedo", ctypes.c_void_p)]
+
+
 class RtDisplayOps(ctypes.Structure):
     _fields_ = [("map", DISPLAY_MAP), ("unmap", DISPLAY_UNMAP)]
 
@@ -206,6 +211,7 @@ SIGNATURES = {
     "rt_unpack_tiles": (_int, [_P, _P, _P, _u32, _u32, _P, _P]),
     "rt_trace_rays": (_int, [_P, _P, _u32, _u32, _P, _P, ctypes.POINTER(RtStats)]),
     "rt_pick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
+    "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),
     "rt_readback": (_int, [_P, _P, _P]),

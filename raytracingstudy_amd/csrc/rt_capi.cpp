@@ -43,6 +43,9 @@ hipError_t launch_cam8_screen(const float4* prim_sp, uint32_t n, const float o[3
 // rt_query.hip: n rays (rt_ray) -> n hits (rt_hit) against a.sc; counters != null: a stats launch
 hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32_t n, bool any,
                         unsigned long long* counters, hipStream_t st);
+// rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
+hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
+                          unsigned long long* counters, hipStream_t st);
 }  // namespace rtamd
 
 using namespace rtamd;
@@ -296,14 +299,19 @@ int set_device(rt_renderer* r) {
     return RT_OK;
 }
 
+// the renderer's intrinsic and pose as the kernels take them
+void fill_camera(const rt_renderer* r, CamArgs& cam) {
+    memcpy(cam.K, r->K, sizeof(r->K));
+    for (int c = 0; c < 3; ++c)
+        for (int row = 0; row < 3; ++row) cam.R[c * 3 + row] = r->pose[c * 4 + row];
+    cam.o[0] = r->pose[12];
+    cam.o[1] = r->pose[13];
+    cam.o[2] = r->pose[14];
+}
+
 void fill_frame_args(rt_renderer* r, FrameArgs& a) {
     memset(&a, 0, sizeof(a));
-    memcpy(a.cam.K, r->K, sizeof(r->K));
-    for (int c = 0; c < 3; ++c)
-        for (int row = 0; row < 3; ++row) a.cam.R[c * 3 + row] = r->pose[c * 4 + row];
-    a.cam.o[0] = r->pose[12];
-    a.cam.o[1] = r->pose[13];
-    a.cam.o[2] = r->pose[14];
+    fill_camera(r, a.cam);
     a.sc = r->sc;
     a.W = r->W;
     a.H = r->H;
@@ -746,6 +754,22 @@ void accum_pixels(rt_renderer* r, const uint32_t* ids, uint32_t n, uint32_t ts) 
     r->accum_sig = sig;
 }
 
+// SceneArgs::prim_al, the albedo of every leaf reference: made once per scene
+// on `st`, by the first frame or G-buffer call that shades from it.
+int ensure_prim_al(rt_renderer* r, SceneArgs& sc, hipStream_t st) {
+    const uint32_t* before = r->d_prim_al.p;
+    int ost;
+    if ((ost = ensure(r, r->d_prim_al, r->prim_slots + kPrimPad))) return ost;
+    if (r->d_prim_al.p != before || r->al_gen != r->scene_gen) {
+        hipError_t e = launch_albedo_refs(sc.prim_idx, sc.albedo, r->prim_slots, r->n_spheres,
+                                          r->d_prim_al.p, st);
+        if (e != hipSuccess) return hip_fail(r, e, "albedo by leaf reference");
+        r->al_gen = r->scene_gen;
+    }
+    sc.prim_al = r->d_prim_al.p;
+    return RT_OK;
+}
+
 // Order work about to be queued on `st` after the renderer's last queued work
 // when that ran on another stream (caller streams are typically non-blocking).
 int order_after_last(rt_renderer* r, hipStream_t st) {
@@ -978,16 +1002,7 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
         a.sc.prim_shd = r->d_prim_shd.p;
         a.sc.prim_shd8 = r->d_prim_shd8.p;
         a.shd_rr = r->shd_rr;
-        // the albedo of every leaf reference, made once per scene
-        const uint32_t* before_a = r->d_prim_al.p;
-        if ((ost = ensure(r, r->d_prim_al, nr))) return ost;
-        if (r->d_prim_al.p != before_a || r->al_gen != r->scene_gen) {
-            hipError_t e = launch_albedo_refs(a.sc.prim_idx, a.sc.albedo, r->prim_slots, r->n_spheres,
-                                              r->d_prim_al.p, st);
-            if (e != hipSuccess) return hip_fail(r, e, "albedo by leaf reference");
-            r->al_gen = r->scene_gen;
-        }
-        a.sc.prim_al = r->d_prim_al.p;
+        if ((ost = ensure_prim_al(r, a.sc, st))) return ost;
     }
     a.counters = ctr;
     const bool scene = r->cfg.mode == RT_MODE_SCENE;
@@ -1624,6 +1639,35 @@ int unpack_tiles_one(rt_renderer* r, const void* dev_packed, const uint32_t* til
     if (e != hipSuccess) return hip_fail(r, e, "rt_unpack_tiles");
     return mark_queued(r, s);
 }
+
+// The query path's own stat lines (rt_trace_rays, rt_render_gbuffer: a stats
+// launch never touches the frames' counter sets): zeroed on `hs` with the
+// start event behind them; after the launch and the end event, read back into
+// `stats` (nodes, tests and ms; the caller adds its ray count).
+constexpr size_t kQueryStatWords = 8 * kStatLineStride;
+int query_stats_begin(rt_renderer* r, hipStream_t hs, unsigned long long*& ctr) {
+    int st;
+    if ((st = ensure(r, r->q_counters, kQueryStatWords))) return st;
+    ctr = r->q_counters.p;
+    RT_HIP(r, hipMemsetAsync(ctr, 0, kQueryStatWords * sizeof(unsigned long long), hs));
+    RT_HIP(r, hipEventRecord(r->ev0, hs));
+    return RT_OK;
+}
+int query_stats_read(rt_renderer* r, const unsigned long long* ctr, rt_stats* stats) {
+    RT_HIP(r, hipEventSynchronize(r->ev1));
+    unsigned long long lines[kQueryStatWords], c[4] = {0, 0, 0, 0};
+    RT_HIP(r, hipMemcpy(lines, ctr, sizeof(lines), hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < 8; ++q)
+        for (uint32_t i = 0; i < 4; ++i) c[i] += lines[q * kStatLineStride + i];
+    float ms = 0.f;
+    RT_HIP(r, hipEventElapsedTime(&ms, r->ev0, r->ev1));
+    memset(stats, 0, sizeof(*stats));
+    stats->nodes_visited = c[2];
+    stats->prims_tested = c[3];
+    stats->ms = ms;
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1652,30 +1696,14 @@ int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kin
     memset(&a, 0, sizeof(a));
     a.sc = r->sc;
     unsigned long long* ctr = nullptr;
-    constexpr size_t kLines = 8 * kStatLineStride;
-    if (stats) {
-        if ((st = ensure(r, r->q_counters, kLines))) return st;
-        ctr = r->q_counters.p;
-        RT_HIP(r, hipMemsetAsync(ctr, 0, kLines * sizeof(unsigned long long), hs));
-        RT_HIP(r, hipEventRecord(r->ev0, hs));
-    }
+    if (stats && (st = query_stats_begin(r, hs, ctr))) return st;
     hipError_t e = launch_query(a, dev_rays, dev_hits, n, kind == RT_QUERY_ANY, ctr, hs);
     if (e != hipSuccess) return hip_fail(r, e, "rt_trace_rays: kernel launch");
     if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
     if ((st = mark_queued(r, hs))) return st;
     if (stats) {
-        RT_HIP(r, hipEventSynchronize(r->ev1));
-        unsigned long long lines[kLines], c[4] = {0, 0, 0, 0};
-        RT_HIP(r, hipMemcpy(lines, ctr, sizeof(lines), hipMemcpyDeviceToHost));
-        for (uint32_t q = 0; q < 8; ++q)
-            for (uint32_t i = 0; i < 4; ++i) c[i] += lines[q * kStatLineStride + i];
-        float ms = 0.f;
-        RT_HIP(r, hipEventElapsedTime(&ms, r->ev0, r->ev1));
-        memset(stats, 0, sizeof(*stats));
+        if ((st = query_stats_read(r, ctr, stats))) return st;
         (kind == RT_QUERY_ANY ? stats->shadow_rays : stats->primary_rays) = n;
-        stats->nodes_visited = c[2];
-        stats->prims_tested = c[3];
-        stats->ms = ms;
     }
     return RT_OK;
 }
@@ -1713,6 +1741,42 @@ int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3
     if (point_out) {
         const float o[3] = {P[12], P[13], P[14]}, d[3] = {wx, wy, wz};
         for (int i = 0; i < 3; ++i) point_out[i] = o[i] + hit_out->t * d[i];
+    }
+    return RT_OK;
+}
+
+// First-hit G-buffer (the reference writes one colour per pixel,
+// src/renderer.cu:57-82).  Like a query it reads scene and camera state only:
+// no frame id, no fill_frame_args (which advances both), the query path's own
+// stat lines, nothing of the frames' counter sets, sums or framebuffer.
+int rt_render_gbuffer(rt_renderer* r, const rt_gbuffer* out, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_render_gbuffer: null handle");
+    if (!out || (!out->dev_hits && !out->dev_normals && !out->dev_albedo))
+        return fail(r, RT_E_INVALID, "rt_render_gbuffer: no output buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_render_gbuffer: no scene (rt_set_scene first)");
+    int st;
+    if ((st = set_device(r))) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    // the kernel's leading argument is a FrameArgs (rt_gbuffer.hip): camera,
+    // scene and size, the rest zero
+    FrameArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_camera(r, a.cam);
+    a.sc = r->sc;
+    a.W = r->W;
+    a.H = r->H;
+    // the frames' own table: whichever of the two runs first makes it
+    if (out->dev_albedo && (st = ensure_prim_al(r, a.sc, hs))) return st;
+    unsigned long long* ctr = nullptr;
+    if (stats && (st = query_stats_begin(r, hs, ctr))) return st;
+    hipError_t e = launch_gbuffer(a, out->dev_hits, out->dev_normals, out->dev_albedo, ctr, hs);
+    if (e != hipSuccess) return hip_fail(r, e, "rt_render_gbuffer: kernel launch");
+    if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
+    if ((st = mark_queued(r, hs))) return st;
+    if (stats) {
+        if ((st = query_stats_read(r, ctr, stats))) return st;
+        stats->primary_rays = static_cast<uint64_t>(r->W) * r->H;
     }
     return RT_OK;
 }

@@ -8,12 +8,14 @@
 //   rt_cli [--config c1|c2|c3|c4|c5] [--width W --height H --spp S --spheres N
 //           --depth D] [--frames F] [--out image.ppm] [--scene in.rtsph]
 //          [--save-scene out.rtsph] [--host-build] [--gpus N [--same-device]]
-//          [--progressive] [--panel] [--walk] [--test-poison]
+//          [--progressive] [--panel] [--walk] [--test-poison] [--gbuffer hits.bin]
 //
 // --panel prints the stats panel (rt_camera.hpp StatsPanel: the reference's
 // ImGui window numbers plus Mrays/s, spp, GPUs) after every frame; --walk
 // moves the camera through the Displayer's controller (W held every frame);
-// --progressive accumulates samples while the camera stays put.
+// --progressive accumulates samples while the camera stays put.  --gbuffer
+// renders the first-hit G-buffer of the last frame's camera (rt_render_gbuffer)
+// and writes its hits as W*H raw little-endian rt_hit records {f32 t, u32 sphere}.
 //
 // --gpus N: one process drives N devices through the C-ABI's
 // multi-device handle (rt_create_multi): device k renders the 64x64 tiles
@@ -24,6 +26,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <hip/hip_runtime_api.h>
 
 #include <chrono>
 #include <string>
@@ -104,7 +108,7 @@ int run_multi(const rt_config& rc, const float pose[16], int gpus, bool same_dev
 }
 
 int main(int argc, char** argv) {
-    std::string cfg = "c2", out, scene_in, scene_out;
+    std::string cfg = "c2", out, scene_in, scene_out, gbuffer_out;
     bool host_build = false, same_device = false, progressive = false, panel = false,
          walk = false, poison = false;
     int gpus = 1;
@@ -130,6 +134,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--out")) out = next("--out");
         else if (!strcmp(argv[i], "--scene")) scene_in = next("--scene");
         else if (!strcmp(argv[i], "--save-scene")) scene_out = next("--save-scene");
+        else if (!strcmp(argv[i], "--gbuffer")) gbuffer_out = next("--gbuffer");
         else if (!strcmp(argv[i], "--host-build")) host_build = true;
         else if (!strcmp(argv[i], "--gpus")) gpus = atoi(next("--gpus")), multi = true;
         else if (!strcmp(argv[i], "--same-device")) same_device = true;
@@ -200,6 +205,7 @@ int main(int argc, char** argv) {
         if (multi) {
             if (gpus < 1 || gpus > RT_MAX_DEVICES) throw rtamd::Error(RT_E_INVALID, "--gpus must be 1..16");
             if (!scene) throw rtamd::Error(RT_E_INVALID, "--gpus needs a scene config");
+            if (!gbuffer_out.empty()) throw rtamd::Error(RT_E_INVALID, "--gbuffer is single-device here");
             return run_multi(rc, pose, gpus, same_device, frames, out, W, H, spp, depth, n,
                              scene_in);
         }
@@ -243,6 +249,34 @@ int main(int argc, char** argv) {
             fprintf(f, "P6\n%d %d\n255\n", W, H);
             for (size_t i = 0; i < (size_t)W * H; ++i) fwrite(&img[4 * i], 1, 3, f);
             fclose(f);
+        }
+        if (!gbuffer_out.empty()) {
+            // after the last frame: the id / depth buffer of the camera it used
+            const size_t npix = (size_t)W * H;
+            void* d_hits = nullptr;
+            if (hipMalloc(&d_hits, npix * sizeof(rt_hit)) != hipSuccess)
+                throw rtamd::Error(RT_E_HIP, "hipMalloc of the hits buffer");
+            std::vector<rt_hit> hits(npix);
+            try {
+                r.renderGBuffer(d_hits);
+                r.synchronize();
+            } catch (...) {
+                (void)hipFree(d_hits);
+                throw;
+            }
+            const hipError_t e = hipMemcpy(hits.data(), d_hits, npix * sizeof(rt_hit), hipMemcpyDeviceToHost);
+            (void)hipFree(d_hits);
+            if (e != hipSuccess) throw rtamd::Error(RT_E_HIP, "hipMemcpy of the hits buffer");
+            size_t n_hit = 0;
+            for (const rt_hit& h : hits) n_hit += h.sphere != RT_NO_HIT;
+            FILE* f = fopen(gbuffer_out.c_str(), "wb");
+            if (!f || fwrite(hits.data(), sizeof(rt_hit), npix, f) != npix) {
+                fprintf(stderr, "cannot write %s\n", gbuffer_out.c_str());
+                if (f) fclose(f);
+                return 1;
+            }
+            fclose(f);
+            printf("gbuffer: %zu of %zu pixels hit a sphere\n", n_hit, npix);
         }
     } catch (const rtamd::Error& e) {
         fprintf(stderr, "rt_cli: %s (code %d)\n", e.what(), e.code);

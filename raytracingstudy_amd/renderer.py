@@ -364,6 +364,47 @@ class KernelRenderer:
         check(self._lib.rt_pick(self._h, float(u), float(v), ctypes.byref(h), _fptr(pt)), self._h)
         return h.sphere != _lib.RT_NO_HIT, float(h.t), int(h.sphere), pt
 
+    # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
+    def render_gbuffer_device(self, hits_ptr: Optional[int] = None, normals_ptr: Optional[int] = None,
+                              albedo_ptr: Optional[int] = None, stream: Optional[int] = None,
+                              stats: bool = False) -> Optional[RtStats]:
+        """rt_render_gbuffer into buffers already on the GPU, each optional, in frame
+        layout (pixel y*W + x): W*H rt_hit (t, sphere) at hits_ptr, W*H float[4]
+        normals at normals_ptr, W*H packed RGBA8 at albedo_ptr.  Asynchronous on
+        `stream` (None: the renderer's own) unless stats."""
+        g = _lib.RtGBuffer(hits_ptr or None, normals_ptr or None, albedo_ptr or None)
+        st = RtStats() if stats else None
+        check(self._lib.rt_render_gbuffer(self._h, ctypes.byref(g),
+                                          ctypes.c_void_p(stream) if stream else None,
+                                          ctypes.byref(st) if st is not None else None), self._h)
+        return st
+
+    def render_gbuffer(self, normals: bool = True, albedo: bool = True, stats: bool = False) -> dict:
+        """The first-hit G-buffer of the current size and camera as host arrays:
+        {"t": (H, W) float32, "sphere": (H, W) uint32[, "normal": (H, W, 4) float32]
+        [, "albedo": (H, W) uint32][, "stats": RtStats]}.  A miss has t = +inf,
+        sphere = RT_NO_HIT, a zero normal and albedo 0."""
+        import torch
+        w, h = self.width, self.height
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_hits = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
+        d_nrm = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if normals else None
+        d_alb = torch.empty((h, w), dtype=torch.int32, device=dev) if albedo else None
+        torch.cuda.synchronize(dev)  # the allocations are torch's
+        st = self.render_gbuffer_device(d_hits.data_ptr(), d_nrm.data_ptr() if normals else None,
+                                        d_alb.data_ptr() if albedo else None, None, stats)
+        self.synchronize()
+        hits = d_hits.cpu().numpy()
+        out = {"t": np.ascontiguousarray(hits[..., 0]).view(np.float32),
+               "sphere": np.ascontiguousarray(hits[..., 1]).view(np.uint32)}
+        if normals:
+            out["normal"] = d_nrm.cpu().numpy()
+        if albedo:
+            out["albedo"] = d_alb.cpu().numpy().view(np.uint32)
+        if stats:
+            out["stats"] = st
+        return out
+
     def reset_accumulation(self) -> None:
         """Progressive mode: the next frame starts from zero samples."""
         check(self._lib.rt_reset_accumulation(self._h), self._h)
