@@ -101,7 +101,7 @@ enum {
      * covering the root box.  Images and counters are the same for all three. */
     RT_FLAG_PAD_FILL_SHIFT = 8,
     /* Test-only: rt_create / rt_create_multi honour the RT_TEST_* environment
-     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY); without
+     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY, RT_TEST_OCC_CAP, RT_TEST_OCC_MEAN); without
      * this flag they are ignored (a set one is named on stderr once). */
     RT_FLAG_TEST_HOOKS = 1u << 10,
     /* Test-only: before every frame, fill the frame's outputs with a sentinel
@@ -109,6 +109,10 @@ enum {
      * progressive frame's sums all-ones bits, a NaN), so a pixel the kernels
      * do not write shows in any readback.  Costs a memset per frame. */
     RT_FLAG_TEST_POISON = 1u << 11,
+    /* A/B: no occluder lists, every shadow ray walks the octree (DESIGN.md 5.1
+     * round 7).  Images and counters are the same either way.  (Its own bit:
+     * the eight RT_FLAG_OPT_SHIFT bits are all taken.) */
+    RT_FLAG_NO_OCCLUDERS = 1u << 12,
     /* bits 16..19: scene-kernel variant for A/B runs (0 = default: 13, the
      * per-wave queue, for spp >= 8, else 7; others in DESIGN.md 5.1); images
      * and counters are identical across variants (packets: images only) */
@@ -169,6 +173,16 @@ typedef struct rt_scene_info {
     double upload_ms;        /* time to place the sphere list in device memory          */
     uint32_t builder;        /* RT_BUILDER_* that built the current tree                */
     uint32_t cell_table_depth; /* K of the depth-K cell table the walk uses, 0 = none   */
+    /* Occluder lists: made by the first frame after a
+     * scene (or light) change, so all three are 0 until then. */
+    double occluder_build_ms;  /* device time of that build; filled at the renderer's next
+                                  synchronisation after it (a stats frame, rt_synchronize,
+                                  rt_readback), 0 until then                            */
+    uint32_t occluder_entries; /* total length of the lists                               */
+    uint32_t occluder_lists_on; /* 1: plain frames answer shadow rays from the lists; 0:
+                                  every shadow ray walks (scene rule, RT_FLAG_NO_OCCLUDERS).
+                                  A frame whose camera is far from the scene (its distance
+                                  terms over 3x the root box's farthest corner) walks too */
 } rt_scene_info;
 
 enum { RT_BUILDER_DEVICE = 0, RT_BUILDER_HOST = 1 };
@@ -223,6 +237,15 @@ int rt_get_scene_info(const rt_renderer* r, rt_scene_info* info);
  * 4*n_prim_refs floats, prim_idx_out n_prim_refs words; any may be NULL. */
 int rt_export_octree(rt_renderer* r, uint32_t* nodes_out, float* prim_sp_out,
                      uint32_t* prim_idx_out);
+/* Copy the occluder lists to host memory (RT_E_STATE when the scene has none,
+ * or before the first frame after a scene change): per sphere offsets_out and
+ * counts_out (n_spheres words each; a count of 0xFFFFFFFF: that sphere's
+ * shadow rays walk the octree and its list is empty), indices_out the lists'
+ * sphere indices (occluder_entries words, nearest-first along the light),
+ * prim_occ_out 2*n_prim_refs words: the {offset, count} header of every leaf
+ * reference.  Any may be NULL. */
+int rt_export_occluders(rt_renderer* r, uint32_t* offsets_out, uint32_t* counts_out,
+                        uint32_t* indices_out, uint32_t* prim_occ_out);
 /* Synthetic scene generator: splitmix64 -> PCG32 from `seed`;
  * centres U[0,1.28)^3, radius 0.02*(1000/n)^(1/3)*U[0.5,1), albedo U[0.2,1). */
 int rt_generate_spheres(uint32_t n, uint32_t seed, float* spheres_out, uint32_t* albedo_out);

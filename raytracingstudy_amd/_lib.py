@@ -38,6 +38,7 @@ RT_TILE_SKIP = 0xFFFFFFFF  # rt_unpack_tiles: a padding slot, not copied
 RT_FLAG_PAD_FILL_SHIFT = 8  # test-only: 0 zeros, 1 NaN, 2 covering spheres after the last leaf
 RT_FLAG_TEST_HOOKS = 1 << 10   # test-only: honour the RT_TEST_* environment variables
 RT_FLAG_TEST_POISON = 1 << 11  # test-only: sentinel-fill every frame's outputs first
+RT_FLAG_NO_OCCLUDERS = 1 << 12  # A/B: every shadow ray walks the octree (no occluder lists)
 RT_FLAG_VARIANT_SHIFT = 16
 RT_FLAG_OPT_SHIFT = 20
 RT_FLAG_CELL_TABLE_SHIFT = 28
@@ -111,6 +112,9 @@ class RtSceneInfo(ctypes.Structure):
         ("upload_ms", ctypes.c_double),
         ("builder", ctypes.c_uint32),
         ("cell_table_depth", ctypes.c_uint32),
+        ("occluder_build_ms", ctypes.c_double),
+        ("occluder_entries", ctypes.c_uint32),
+        ("occluder_lists_on", ctypes.c_uint32),
     ]
 
     def as_dict(self) -> dict:
@@ -201,6 +205,7 @@ SIGNATURES = {
     "rt_set_octree": (_int, [_P, _fp, _fp, ctypes.c_float]),
     "rt_get_scene_info": (_int, [_P, ctypes.POINTER(RtSceneInfo)]),
     "rt_export_octree": (_int, [_P, _P, _P, _P]),
+    "rt_export_occluders": (_int, [_P, _P, _P, _P, _P]),
     "rt_save_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32]),
     "rt_load_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32, ctypes.POINTER(_u32)]),
     "rt_generate_spheres": (_int, [_u32, _u32, _P, _P]),

@@ -103,4 +103,71 @@ private:
     uint32_t k_ = 0;
 };
 
+// Occluder lists (occluder.hip): for every sphere the
+// spheres that can occlude a shadow ray leaving it along the light direction,
+// found over a uniform grid on the light plane.  Two stages around the one
+// wait the light-plane records already make: count() queues the counting
+// passes and the totals' readback, the caller synchronises the stream, and
+// fill() decides the scene rule from the totals, allocates and queues the
+// fill, the sort and the per-reference headers (no further wait).
+class OccluderLists {
+public:
+    struct Totals {
+        unsigned long long work;   // pair tests the cell histogram bounds
+        unsigned long long cand;   // candidates over all spheres (uncapped)
+        uint32_t entries;          // list entries (spheres over the cap hold none)
+        uint32_t n_bad;            // spheres with r <= 0 or a non-finite value
+        uint32_t n_capped;         // spheres over the cap ("walk" headers)
+        uint32_t skipped;          // 1: the pair passes did not run (n_bad or work)
+    };
+    OccluderLists() = default;
+    OccluderLists(const OccluderLists&) = delete;
+    OccluderLists& operator=(const OccluderLists&) = delete;
+    ~OccluderLists() { release(); }
+    hipError_t count(const float4* spheres, uint32_t n, const float L[3], const float e[6],
+                     double delta, double M, uint32_t cap, hipStream_t st);
+    hipError_t fill(const uint32_t* prim_idx, uint32_t n_refs, double mean_max, hipStream_t st);
+    void release();
+    void off() { on_ = false; }
+    bool on() const { return on_; }
+    const Totals& totals() const { return tot_; }
+    const uint2* prim_occ() const { return on_ ? prim_occ_ : nullptr; }
+    const float4* occ_sp() const { return on_ ? occ_sp_ : nullptr; }
+    const uint2* headers() const { return hdr_; }      // by sphere index {offset, count | kOccWalk}
+    const uint32_t* occ_idx() const { return occ_idx_; }  // the lists' sphere indices
+    uint32_t n() const { return n_; }
+
+private:
+    template <typename T>
+    hipError_t reserve(T*& p, size_t& cap, size_t n);
+    hipError_t scan(uint32_t* data, uint32_t n, hipStream_t st);
+    const float4* spheres_ = nullptr;
+    uint32_t n_ = 0, cap_ = 0, gmax_ = 0;
+    bool on_ = false;
+    Totals tot_{};
+    double* geo_ = nullptr;       // per sphere {u, v, w, R, sr, r}
+    size_t geo_cap_ = 0;
+    uint32_t* cell_of_ = nullptr;
+    size_t cell_of_cap_ = 0;
+    uint32_t* cells_ = nullptr;   // [0, nc]: starts (after the scan), [nc + 1, 2 nc + 1): cursors
+    size_t cells_cap_ = 0;
+    uint32_t* items_ = nullptr;
+    size_t items_cap_ = 0;
+    uint32_t* len_ = nullptr;     // per sphere: list length, then offset (after the scan)
+    size_t len_cap_ = 0;
+    uint32_t* part_ = nullptr;    // the scan's block sums
+    size_t part_cap_ = 0;
+    uint2* hdr_ = nullptr;
+    size_t hdr_cap_ = 0;
+    void* par_ = nullptr;         // grid parameters and totals (device)
+    float4* occ_sp_ = nullptr;
+    size_t occ_sp_cap_ = 0;
+    uint32_t* occ_idx_ = nullptr;
+    size_t occ_idx_cap_ = 0;
+    double* keys_ = nullptr;
+    size_t keys_cap_ = 0;
+    uint2* prim_occ_ = nullptr;
+    size_t prim_occ_cap_ = 0;
+};
+
 }  // namespace rtamd

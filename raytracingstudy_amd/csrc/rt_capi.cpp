@@ -216,6 +216,17 @@ struct rt_renderer {
     // albedo by leaf reference (SceneArgs::prim_al) and the scene it was made for
     DevBuf<uint32_t> d_prim_al;
     uint64_t al_gen = ~0ull;
+    // occluder lists (SceneArgs::prim_occ / occ_sp, occluder.hip): built with
+    // the light-plane records, for the same scene and light; occ_cap: the
+    // per-sphere cap (kOccCap, or RT_TEST_OCC_CAP under RT_FLAG_TEST_HOOKS);
+    // occ_e0 / occ_e1 time the build (collected at the renderer's next
+    // synchronisation, occ_collect_time); occ_M: the M the lists were made with
+    OccluderLists occ;
+    uint32_t occ_cap = kOccCap;
+    double occ_mean_max = kOccMeanMax;  // (RT_TEST_OCC_MEAN under RT_FLAG_TEST_HOOKS)
+    hipEvent_t occ_e0 = nullptr, occ_e1 = nullptr;
+    bool occ_timed = false;
+    double occ_M = 0.0;
     // ray queries (rt_trace_rays, rt_pick): their own stat lines (a query never
     // touches the frames' counter sets) and rt_pick's one ray and one hit
     DevBuf<unsigned long long> q_counters;
@@ -681,6 +692,8 @@ int build_scene(rt_renderer* r) {
     in.prim_bytes = sizeof(float4) + sizeof(uint32_t);
     in.build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     ++r->scene_gen;  // the camera-relative screen records are remade at the next frame
+    r->occ.off();    // and the occluder lists with the light-plane records
+    r->occ_timed = false;
     r->has_scene = true;
     return RT_OK;
 }
@@ -789,6 +802,16 @@ int mark_queued(rt_renderer* r, hipStream_t st) {
 // new value is reported once.  A plain host read: rt_render calls it before
 // every frame with no sync, rt_synchronize / rt_readback / stats frames after
 // theirs.
+// The occluder build's device time into info.occluder_build_ms: called where
+// the renderer has just synchronised (stats frames, rt_synchronize,
+// rt_readback), once the build's last kernel is done; never waits.
+void occ_collect_time(rt_renderer* r) {
+    if (!r->occ_timed || hipEventQuery(r->occ_e1) != hipSuccess) return;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, r->occ_e0, r->occ_e1) == hipSuccess) r->info.occluder_build_ms = ms;
+    r->occ_timed = false;
+}
+
 int queue_report(rt_renderer* r) {
     const uint32_t v = __atomic_load_n(r->qerr_host, __ATOMIC_ACQUIRE);
     if (v == r->qerr_seen) return RT_OK;
@@ -994,7 +1017,35 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
             // the 8-byte records' radius term, once per scene and light (a sync)
             uint32_t bits = 0;
             RT_HIP(r, hipMemcpyAsync(&bits, r->d_shd_rr.p + nbk, sizeof(bits), hipMemcpyDeviceToHost, st));
+            // the occluder lists of this scene and light (DESIGN.md 5.1 round
+            // 7): the counting passes and their totals ride on the same wait,
+            // the fill is queued after it
+            const bool want_occ = !(r->cfg.flags & RT_FLAG_NO_OCCLUDERS) && a.shadows;
+            r->occ.off();
+            r->occ_timed = false;
+            r->info.occluder_build_ms = 0.0;
+            r->info.occluder_entries = 0;
+            r->info.occluder_lists_on = 0;
+            if (want_occ) {
+                RT_HIP(r, hipEventRecord(r->occ_e0, st));
+                e = r->occ.count(r->d_spheres.p, r->n_spheres, a.L, a.shd_e, delta, m + 1e-4,
+                                 r->occ_cap, st);
+                if (e != hipSuccess) {
+                    // the copy into `bits` (and count()'s own) may be queued: wait before leaving
+                    (void)hipStreamSynchronize(st);
+                    return hip_fail(r, e, "occluder lists (count)");
+                }
+                r->occ_M = m + 1e-4;
+            }
             RT_HIP(r, hipStreamSynchronize(st));
+            if (want_occ) {
+                e = r->occ.fill(a.sc.prim_idx, r->prim_slots, r->occ_mean_max, st);
+                if (e != hipSuccess) return hip_fail(r, e, "occluder lists (fill)");
+                RT_HIP(r, hipEventRecord(r->occ_e1, st));
+                r->occ_timed = true;
+                r->info.occluder_lists_on = r->occ.on() ? 1u : 0u;
+                r->info.occluder_entries = r->occ.on() ? r->occ.totals().entries : 0u;
+            }
             memcpy(&r->shd_rr, &bits, sizeof(bits));
             memcpy(r->shd_e, a.shd_e, sizeof(r->shd_e));
             r->shd_gen = r->scene_gen;
@@ -1002,6 +1053,27 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
         a.sc.prim_shd = r->d_prim_shd.p;
         a.sc.prim_shd8 = r->d_prim_shd8.p;
         a.shd_rr = r->shd_rr;
+        a.sc.prim_occ = r->occ.prim_occ();
+        a.sc.occ_sp = r->occ.occ_sp();
+        if (a.sc.prim_occ) {
+            // The lists' bounds (R_i, the self-exclusion) hold the rounding
+            // of the hit point p = o_cam + t d, which grows with the camera's
+            // distance: they were derived for |o_cam| + (the camera's
+            // distance to the root box's farthest corner) <= kOccCamGate M
+            // (DESIGN.md 5.1 round 7).  A frame from farther away (or from a
+            // non-finite origin) walks: the kOcc = false instances.
+            double far2 = 0.0, o2 = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                const double o = a.cam.o[i];
+                const double d = std::max(fabs(o - r->info.root_min[i]), fabs(o - r->info.root_max[i]));
+                far2 += d * d;
+                o2 += o * o;
+            }
+            if (!(sqrt(o2) + sqrt(far2) <= kOccCamGate * r->occ_M)) {
+                a.sc.prim_occ = nullptr;
+                a.sc.occ_sp = nullptr;
+            }
+        }
         if ((ost = ensure_prim_al(r, a.sc, st))) return ost;
     }
     a.counters = ctr;
@@ -1077,6 +1149,7 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
     if (stats) {
         RT_HIP(r, hipEventRecord(r->ev1, st));
         RT_HIP(r, hipEventSynchronize(r->ev1));
+        occ_collect_time(r);
         unsigned long long lines[8 * kStatLineStride], c[4] = {0, 0, 0, 0};
         RT_HIP(r, hipMemcpy(lines, ctr + kStatLineBase, sizeof(lines), hipMemcpyDeviceToHost));
         for (uint32_t q = 0; q < 8; ++q)
@@ -1174,6 +1247,11 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
     // test only (tests/test_gpu_variants.py, test_gpu_queue_report.py)
     if (const char* cd = test_env(cfg->flags, "RT_TEST_CLAIM_DELAY"))
         r->test_claim_delay = static_cast<uint32_t>(std::min(100000ul, strtoul(cd, nullptr, 10)));
+    // test only (tests/test_gpu_occluders.py): the per-sphere cap of the occluder lists
+    if (const char* oc = test_env(cfg->flags, "RT_TEST_OCC_CAP"))
+        r->occ_cap = static_cast<uint32_t>(std::min<unsigned long>(kOccCapMax, strtoul(oc, nullptr, 10)));
+    // ... and the scene rule's mean candidate count (a dense test scene on lists)
+    if (const char* om = test_env(cfg->flags, "RT_TEST_OCC_MEAN")) r->occ_mean_max = strtod(om, nullptr);
     if (const char* fe = test_env(cfg->flags, "RT_TEST_FAULT"))
         r->test_fault_queue = strcmp(fe, "queue:0") == 0;
     // src/renderer.cu:87-89: K0 = mat3(1000,0,640, 0,1000,340, 0,0,1), pose = mat4(1)
@@ -1186,6 +1264,8 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&r->ev0);
     if (e == hipSuccess) e = hipEventCreate(&r->ev1);
+    if (e == hipSuccess) e = hipEventCreate(&r->occ_e0);
+    if (e == hipSuccess) e = hipEventCreate(&r->occ_e1);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done, hipEventDisableTiming);
     // the frame-failure word: pinned, host-coherent, mapped for the kernels
     if (e == hipSuccess)
@@ -1252,6 +1332,9 @@ int rt_destroy(rt_renderer* r) {
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();
+    r->occ.release();
+    if (r->occ_e0) (void)hipEventDestroy(r->occ_e0);
+    if (r->occ_e1) (void)hipEventDestroy(r->occ_e1);
     if (r->ev0) (void)hipEventDestroy(r->ev0);
     if (r->ev1) (void)hipEventDestroy(r->ev1);
     if (r->done) (void)hipEventDestroy(r->done);
@@ -1409,6 +1492,33 @@ int rt_get_scene_info(const rt_renderer* r, rt_scene_info* info) {
     if (!r || !info) return RT_E_INVALID;
     if (!r->has_scene) return RT_E_NOSCENE;
     *info = r->info;
+    return RT_OK;
+}
+
+int rt_export_occluders(rt_renderer* r, uint32_t* offsets_out, uint32_t* counts_out,
+                        uint32_t* indices_out, uint32_t* prim_occ_out) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_export_occluders: null handle");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_export_occluders: no scene");
+    if (!r->occ.on() || r->shd_gen != r->scene_gen)
+        return fail(r, RT_E_STATE, "rt_export_occluders: the scene has no occluder lists "
+                                   "(they are made by the first frame after a scene change)");
+    if (prim_occ_out && r->leaf_packed)
+        return fail(r, RT_E_STATE, "rt_export_occluders: no per-reference export of a line-packed layout");
+    int st;
+    if ((st = set_device(r))) return st;
+    RT_HIP(r, hipDeviceSynchronize());
+    const uint32_t n = r->occ.n(), m = r->occ.totals().entries;
+    std::vector<uint2> hdr(n);
+    if (n) RT_HIP(r, hipMemcpy(hdr.data(), r->occ.headers(), n * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (offsets_out) offsets_out[i] = hdr[i].x;
+        if (counts_out) counts_out[i] = hdr[i].y;
+    }
+    if (indices_out && m)
+        RT_HIP(r, hipMemcpy(indices_out, r->occ.occ_idx(), m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (prim_occ_out && r->info.n_prim_refs)
+        RT_HIP(r, hipMemcpy(prim_occ_out, r->occ.prim_occ(), r->info.n_prim_refs * sizeof(uint2),
+                            hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1797,6 +1907,7 @@ int rt_synchronize(rt_renderer* r) {
     if ((st = set_device(r))) return st;
     RT_HIP(r, hipStreamSynchronize(r->stream));
     if (r->pending) RT_HIP(r, hipEventSynchronize(r->done));
+    occ_collect_time(r);
     return queue_report(r);
 }
 
@@ -1808,6 +1919,7 @@ int rt_readback(rt_renderer* r, uint8_t* host_rgba8, float* host_rgba32f) {
     // the frame may have been queued on a caller's stream
     RT_HIP(r, hipStreamSynchronize(r->stream));
     if (r->pending) RT_HIP(r, hipEventSynchronize(r->done));
+    occ_collect_time(r);
     if ((st = queue_report(r))) return st;
     const size_t px = (size_t)r->W * r->H;
     if (host_rgba8) RT_HIP(r, hipMemcpy(host_rgba8, r->fb.p, px * 4, hipMemcpyDeviceToHost));

@@ -198,7 +198,7 @@ __device__ __forceinline__ uint32_t hit_albedo(SA& S, uint32_t h) {
 
 // Unified lane path: one walk instance run twice (primary, then the shadow ray
 // of the lanes that need one), so the register allocator sees one walk.
-template <int kChunk, bool kStats, bool kCam8 = false>
+template <int kChunk, bool kStats, bool kCam8 = false, bool kOcc = false>
 __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uint32_t x,
                                                          uint32_t y, uint32_t hp, uint32_t s,
                                                          bool valid, uint32_t& n_shadow,
@@ -223,6 +223,7 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
     bool active = valid, hit0 = false;
     float lam = 0.0f;
     uint32_t al = 0;
+    uint2 occ_hdr = make_uint2(0u, 0u);  // kOcc: the hit sphere's occluder-list header
     // the primary and the shadow walk as two instances (the phase loop was
     // always unrolled into two copies; written out so that the primary one
     // keeps the camera-relative screen, a compile-time choice)
@@ -238,7 +239,10 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                 hit = walk<false, kChunk, false, kStats, false, false, kCam8>(S, r0, r1, r2, d0, d1, d2, 0.0f, INFINITY, t,
                                                          idx, n_nodes, n_prims,
                                                          static_cast<uint2*>(stk), false, bs, lbs);
-            else {
+            else if (kOcc) {
+                // answered from the hit sphere's occluder list (round 7)
+                hit = shadow_occluded<false>(S, occ_hdr, true, r0, r1, r2, static_cast<uint2*>(stk), lbs);
+            } else {
                 // the shadow direction L is the frame's, the same in every
                 // lane: read afresh from the kernel arguments (SGPRs), not the
                 // lanes' d registers
@@ -267,6 +271,7 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                 lam = ndl > 0.0f ? ndl : 0.0f;
                 want_shadow = ndl > 0.0f && kb->shadows;
                 al = hit_albedo(kb->sc, idx);
+                if (kOcc && want_shadow) occ_hdr = kb->sc.prim_occ[idx];
                 r0 = p0 + n0 * kShadowEps;
                 r1 = p1 + n1 * kShadowEps;
                 r2 = p2 + n2 * kShadowEps;
@@ -298,7 +303,7 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
 // live across the walks instead of the slot and the tile-local origin).
 // Rounds of spw samples, pairwise butterfly per round, rounds added in
 // order in the leader's LDS slot, then the mean is written.
-template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kCam8 = false>
+template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kCam8 = false, bool kOcc = false>
 __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc, void* stk,
                                                 uint32_t ox, uint32_t oy, uint32_t obase,
                                                 uint32_t& n_primary,
@@ -326,7 +331,7 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
         const uint32_t sg = r * spw + sub_base;
         const bool valid = lane_ok && sg < s_end;
         n_primary += static_cast<uint32_t>(__popcll(__ballot(valid)));  // wave-uniform
-        PixelOut c = sample_color_unified<kChunk, kStats, kCam8>(a, x, y, hp, sg, valid, n_shadow,
+        PixelOut c = sample_color_unified<kChunk, kStats, kCam8, kOcc>(a, x, y, hp, sg, valid, n_shadow,
                                                           n_nodes, n_prims, stk, bs, lbs);
         // Pixel sum of this round: pairwise butterfly over the pixel's g
         // lanes (missing samples are 0) = oracle.c:tree_sum; rounds are then
@@ -440,7 +445,7 @@ __device__ __forceinline__ HitShade hit_shade(float d0, float d1, float d2, floa
 //     samples of all rounds together, in quadrant order), each recomputing
 //     its hit point from {t, sphere} with the same operations;
 //  4. per round in sample order: colours, pairwise sums, rounds in order.
-template <bool kTiles, int kChunk, bool kStats, bool kProg>
+template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kOcc = false>
 __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl, void* stk,
                                                    uint32_t x, uint32_t y, uint32_t obase,
                                                    uint32_t& n_primary, uint32_t& n_shadow,
@@ -541,11 +546,13 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         const uint32_t sl = has ? static_cast<uint32_t>(lit[j]) : 0u;
         float o0 = 0.f, o1 = 0.f, o2 = 0.f, lam = 0.0f;
         uint32_t idx = 0;
+        uint2 occ_hdr = make_uint2(0u, 0u);
         if (has) {
             float d0, d1, d2;
             sample_dir(x, y, hp, s_base + sl, d0, d1, d2);
             const uint2 sv = slot[sl];
             idx = sv.y;
+            if (kOcc) occ_hdr = kernargs()->sc.prim_occ[idx];
             const HitShade h = hit_shade(d0, d1, d2, __uint_as_float(sv.x), idx, bs);
             lam = h.ndl > 0.0f ? h.ndl : 0.0f;
             o0 = h.p0 + h.n0 * kShadowEps;
@@ -553,7 +560,10 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
             o2 = h.p2 + h.n2 * kShadowEps;
         }
         bool occ = false;
-        if (has) {
+        if (kOcc) {
+            // answered from the hit spheres' occluder lists (round 7)
+            occ = shadow_occluded<true>(S, occ_hdr, has, o0, o1, o2, static_cast<uint2*>(stk), lbs);
+        } else if (has) {
             RT_BS(kBsPhase);
             RT_BS(kBsPhaseShadow);
             KernArgs* kl = kernargs();
@@ -648,8 +658,9 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
 // and 72: the extra spills cost more; profiles/r02/sgpr_ab.log).
 // scene_kernel_w8 below is that build of the timed default.
 template <bool kTiles, int kChunk, bool kStats = true, bool kProg = false, bool kWaveQ = false,
-          bool kSort = false>
+          bool kSort = false, bool kOcc = false>
 __device__ __forceinline__ void scene_body(FrameArgs a) {
+    static_assert(!kOcc || !kStats, "stats frames walk: their counters are the oracle's");
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
     float4* acc = lds;  // [256] running pixel sums (leader lanes' slots)
     const uint32_t wave = threadIdx.x >> 6;
@@ -847,10 +858,10 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
                 const unsigned long long tu0 = wall_clock64();
 #endif
                 if (kSort)
-                    shade_pixel_sorted<kTiles, kChunk, kStats, kProg>(
+                    shade_pixel_sorted<kTiles, kChunk, kStats, kProg, kOcc>(
                         a, wl, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs, lbs);
                 else
-                    shade_wave_tile<kTiles, kChunk, kStats, kProg, RT_CAM8 != 0 && !kSort>(
+                    shade_wave_tile<kTiles, kChunk, kStats, kProg, RT_CAM8 != 0 && !kSort, kOcc>(
                         a, acc, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs, lbs);
 #ifdef RT_TIMELINE
                 // per unit {start, end, hw_id << 32 | xcc << 16 | wave index}
@@ -903,7 +914,7 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
 #ifdef RT_TIMELINE
                 const unsigned long long tu0 = wall_clock64();
 #endif
-                shade_wave_tile<kTiles, kChunk, kStats, kProg>(
+                shade_wave_tile<kTiles, kChunk, kStats, kProg, false, kOcc>(
                     a, acc, stk, ox + wox, oy + woy, obase, n_primary, n_shadow, n_nodes,
                     n_prims, bs, lbs);
 #ifdef RT_TIMELINE
@@ -945,17 +956,18 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
 }
 
 template <bool kTiles, int kMinW, int kChunk, bool kStats = true, bool kProg = false,
-          bool kWaveQ = false, bool kSort = false>
+          bool kWaveQ = false, bool kSort = false, bool kOcc = false>
 __global__ void __launch_bounds__(kBlockThreads, kMinW) scene_kernel(FrameArgs a) {
-    scene_body<kTiles, kChunk, kStats, kProg, kWaveQ, kSort>(a);
+    scene_body<kTiles, kChunk, kStats, kProg, kWaveQ, kSort, kOcc>(a);
 }
 
 // The timed default for spp >= 8 (variant 13, plain frames): 8 waves per SIMD,
 // SGPRs capped so that they fit (see above).
-template <bool kTiles, bool kProg = false, bool kSort = false>
+// kOcc: shadow rays answered from the occluder lists (a scene that has them)
+template <bool kTiles, bool kProg = false, bool kSort = false, bool kOcc = false>
 __global__ void __launch_bounds__(kBlockThreads, 8) __attribute__((amdgpu_num_sgpr(80)))
     scene_kernel_w8(FrameArgs a) {
-    scene_body<kTiles, 2, false, kProg, true, kSort>(a);
+    scene_body<kTiles, 2, false, kProg, true, kSort, kOcc>(a);
 }
 
 // Camera-relative screen records of every leaf reference (and the kPrimPad
@@ -1329,19 +1341,21 @@ static bool sorted_rounds(const FrameArgs& a) {
            (a.accum != nullptr || a.variant == kVariantWaveQ);
 }
 
-template <bool kTiles>
-static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStream_t st) {
+// kOcc: the plain (counter-free) instances answer shadow rays from the
+// scene's occluder lists; stats frames walk either way
+template <bool kTiles, bool kOcc>
+static void launch_scene_o(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStream_t st) {
     if (sorted_rounds(a)) {
         const size_t sl = sort_lds_bytes(a);
         if (a.accum) {
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, true, true, true>, a, sl, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, true, true>, a, sl, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, true, true, kOcc>, a, sl, st, 8);
         } else if (a.count_work) {
             launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true, true>, a, sl, st);
         } else {
-            launch_waveq(scene_kernel_w8<kTiles, false, true>, a, sl, st, 8);
+            launch_waveq(scene_kernel_w8<kTiles, false, true, kOcc>, a, sl, st, 8);
         }
         return;
     }
@@ -1350,11 +1364,11 @@ static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, true, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, true>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, true, false, kOcc>, a, lds, st, 8);
         } else if (a.count_work) {
             launch_persistent(scene_kernel<kTiles, 1, 2, true, true>, a, n_bt, lds, st);
         } else {
-            launch_persistent(scene_kernel<kTiles, 1, 2, false, true>, a, n_bt, lds, st);
+            launch_persistent(scene_kernel<kTiles, 1, 2, false, true, false, false, kOcc>, a, n_bt, lds, st);
         }
         return;
     }
@@ -1366,7 +1380,7 @@ static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
             if (a.count_work)
                 launch_persistent(scene_kernel<kTiles, 1, 2, true>, a, n_bt, lds, st);
             else
-                launch_persistent(scene_kernel<kTiles, 1, 2, false>, a, n_bt, lds, st);
+                launch_persistent(scene_kernel<kTiles, 1, 2, false, false, false, false, kOcc>, a, n_bt, lds, st);
             break;
         case kVariantWaveQLow:  // the spp < 8 default (round 4): the per-wave queue, 8 waves/SIMD
             // No workgroup barrier per block tile: the timeline of the block-tile
@@ -1379,7 +1393,7 @@ static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc>, a, lds, st, 8);
             break;
         case kVariantWaveQ:  // the spp >= 8 default: per-wave scheduling over per-XCD queues.
             // Timed (plain) frames: 8 waves/SIMD with SGPRs capped at 80
@@ -1388,7 +1402,7 @@ static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc>, a, lds, st, 8);
             break;
         default:  // rejected by variant_available() before any launch
             break;
@@ -1399,6 +1413,14 @@ static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
 // measured-and-rejected alternatives of DESIGN.md 5.1 (packets, LDS / scalar /
 // one-lane uniform leaves, bundle prefilter, 6- and 8-wave builds) were
 // removed in round 3; their A/B logs stay under profiles/.
+template <bool kTiles>
+static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStream_t st) {
+    if (a.sc.prim_occ && a.sc.occ_sp && a.shadows && !a.count_work)
+        launch_scene_o<kTiles, true>(a, n_bt, lds, st);
+    else
+        launch_scene_o<kTiles, false>(a, n_bt, lds, st);
+}
+
 bool variant_available(uint32_t v) {
     return v == 0 || v == kVariantLaneUnified || v == kVariantLaneUnified2NoStats ||
            v == kVariantWaveQ || v == kVariantWaveQLow;

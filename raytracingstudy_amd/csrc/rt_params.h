@@ -219,7 +219,47 @@ struct SceneArgs {
     // off at run time loses on every config, C5d included,
     // profiles/r05/stage_switch_ab.log)
     uint32_t lds_max;
+    // Occluder lists (occluder.hip): per leaf reference
+    // a header {offset, count} into occ_sp, the sphere records that can
+    // occlude a shadow ray leaving that reference's sphere along L (made once
+    // per scene and light); count == kOccWalk: that sphere's rays walk the
+    // octree.  Null: the scene has no lists and every shadow ray walks.
+    const uint2* prim_occ;
+    const float4* occ_sp;
 };
+
+constexpr uint32_t kOccWalk = 0xFFFFFFFFu;  // occluder header count: "walk the octree"
+// Occluder-list limits: a sphere with more than
+// kOccCap candidates walks; a scene whose mean candidate count exceeds
+// kOccMeanMax, or whose arrays exceed kOccMaxBytes, gets no lists; the pair
+// passes are skipped when the cell histogram bounds their work above
+// kOccWorkPerSphere tests a sphere.
+constexpr uint32_t kOccCap = 32;
+constexpr uint32_t kOccCapMax = 64;  // the largest cap a test hook may ask for
+constexpr double kOccMeanMax = 64.0;
+constexpr unsigned long long kOccMaxBytes = 1ull << 30;
+constexpr unsigned long long kOccWorkPerSphere = 2048;
+// Slack of the occluder pair rule: a shadow origin
+// made from a hit on sphere i lies within
+//   R_i = r_i (1 + kOccRel) + kShadowEps (1 + kOccNormM u M / r_i) + kOccAbsM u M
+// of its centre; a sphere is "not wholly behind" with kOccBehindR extra radii.
+constexpr double kOccRel = 1e-4;
+constexpr double kOccNormM = 64.0;
+constexpr double kOccAbsM = 128.0;
+constexpr double kOccBehindR = 1.0;
+// The bounds above hold the rounding of the hit point, at most kOccCamK u Mc
+// with Mc = |o_cam| + the camera's distance to the root box's farthest corner
+// (DESIGN.md 5.1 round 7): frames with Mc <= kOccCamGate M use the lists
+// (kOccCamK kOccCamGate = 42 <= kOccNormM, kOccAbsM), frames from farther
+// away walk (decided per frame on the host, rt_capi.cpp).
+constexpr double kOccCamK = 14.0;
+constexpr double kOccCamGate = 3.0;
+// sphere i stays out of its own list iff
+// kOccSelfM u (r_i + M) <= 0.75 kShadowEps  (kOccSelfM >= kOccCamK kOccCamGate + 6)
+constexpr double kOccSelfM = 48.0;
+static_assert(kOccCamK * kOccCamGate <= kOccNormM && kOccCamK * kOccCamGate <= kOccAbsM &&
+                  kOccCamK * kOccCamGate + 6.0 <= kOccSelfM,
+              "the list bounds cover every camera inside the gate");
 
 // Spheres per wave in the LDS leaf buffer (a leaf of >= kLeafBuf uses global loads)
 constexpr uint32_t kLeafBuf = 32;

@@ -763,4 +763,45 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
     return false;
 }
 
+// The octree walk of the shadow rays whose sphere has no occluder list (a
+// "walk" header).  Inlined: out of line the callee is allocated without the
+// kernel's 64-VGPR budget and the kernel inherits its count (5 waves per SIMD).
+template <bool kNoStack>
+__device__ __forceinline__ bool shadow_walk_fallback(const SceneArgs& S, float o0, float o1, float o2,
+                                                  uint2* __restrict__ stk, uint32_t lb_u) {
+    KernArgs* kl = kernargs();
+    float ts;
+    uint32_t is, nn = 0, np = 0;
+    return walk<true, RT_SHD_CHUNK, false, false, kNoStack, true>(
+        S, o0, o1, o2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, ts, is, nn, np, stk, true,
+        nullptr, lb_u);
+}
+
+// A frame's shadow ray from a hit on the sphere of leaf reference `ref`,
+// answered from that sphere's occluder list (SceneArgs::prim_occ / occ_sp,
+// DESIGN.md 5.1 round 7): the list holds every sphere isect can accept from
+// an origin made on that sphere, so the OR of isect over it (the walk's own
+// exact test, same operands) is the walk's answer.  `hdr` = prim_occ[ref],
+// loaded by the caller; lanes whose header says "walk" walk the octree.
+template <bool kNoStack>
+__device__ __forceinline__ bool shadow_occluded(const SceneArgs& S, uint2 hdr, bool active, float o0,
+                                                float o1, float o2, uint2* __restrict__ stk,
+                                                uint32_t lb_u) {
+    KernArgs* kl = kernargs();
+    const float l0 = kl->L[0], l1 = kl->L[1], l2 = kl->L[2];
+    const bool walks = active && hdr.y == kOccWalk;
+    const uint32_t cnt = active && !walks ? hdr.y : 0u;
+    const float4* __restrict__ lst = kl->sc.occ_sp + hdr.x;
+    bool occ = false;
+    for (uint32_t k = 0; k < cnt && !occ; ++k) {
+        const float4 sp = lst[k];
+        float th;
+        occ = isect(o0, o1, o2, l0, l1, l2, sp, 0.0f, INFINITY, th);
+    }
+    if (__any(walks)) {
+        if (walks) occ = shadow_walk_fallback<kNoStack>(S, o0, o1, o2, stk, lb_u);
+    }
+    return occ;
+}
+
 }  // namespace rtamd

@@ -108,7 +108,7 @@ class KernelRenderer:
                  light_dir: Sequence[float] = (1.0, 1.0, -1.0), ambient: float = 0.1,
                  variant: int = 0, opt_off: int = 0, host_build: bool = False,
                  progressive: bool = False, cell_table: Optional[int] = None,
-                 compat_fma: bool = False, pad_fill: int = 0,
+                 compat_fma: bool = False, pad_fill: int = 0, occluders: bool = True,
                  devices: Optional[Sequence[int]] = None, transport: str = "auto"):
         """devices: render every frame across these HIP devices of this process
         (rt_create_multi: tiles round-robin, slabs gathered to devices[0] over
@@ -137,6 +137,8 @@ class KernelRenderer:
             flags |= RT_FLAG_PROGRESSIVE
         if compat_fma:
             flags |= _lib.RT_FLAG_COMPAT_FMA
+        if not occluders:  # A/B: every shadow ray walks the octree
+            flags |= _lib.RT_FLAG_NO_OCCLUDERS
         # pad_fill (test-only): 0 zeros, 1 NaN, 2 covering spheres after the last leaf list
         if not 0 <= int(pad_fill) <= 2:
             raise ValueError("pad_fill must be 0, 1 or 2")
@@ -273,6 +275,20 @@ class KernelRenderer:
         idx = np.zeros(max(m, 1), np.uint32)
         check(self._lib.rt_export_octree(self._h, _vptr(nodes), _vptr(sp), _vptr(idx)), self._h)
         return nodes[:info["n_nodes"]], sp[:m], idx[:m]
+
+    def export_occluders(self):
+        """The occluder lists as host arrays (rt_export_occluders): per sphere
+        offsets and counts (0xFFFFFFFF: that sphere's shadow rays walk), the
+        lists' sphere indices, and the (m, 2) per-reference headers."""
+        info = self.scene_info()
+        n, m, e = info["n_spheres"], info["n_prim_refs"], info["occluder_entries"]
+        off = np.zeros(max(n, 1), np.uint32)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        idx = np.zeros(max(e, 1), np.uint32)
+        refs = np.zeros((max(m, 1), 2), np.uint32)
+        check(self._lib.rt_export_occluders(self._h, _vptr(off), _vptr(cnt), _vptr(idx), _vptr(refs)),
+              self._h)
+        return off[:n], cnt[:n], idx[:e], refs[:m]
 
     def scene_info(self) -> dict:
         info = RtSceneInfo()

@@ -1,0 +1,422 @@
+"""Occluder lists: plain frames answer shadow rays from
+per-sphere lists of the spheres that can occlude a ray leaving that sphere
+along the light, built once per scene and light (csrc/occluder.hip).
+
+The lists' contents against the pair rule restated here in numpy f64, their
+soundness against the oracle's any-hit walk and brute force, and frames of the
+two algorithms (plain = lists, stats = walk) against each other and the oracle.
+
+Scenes: "U", 3,000 generator spheres; "K", 1,500 spheres in one Gaussian
+cluster (sigma 0.03, the generator's radii for n = 1,500).  K's candidate
+lists average ~200 spheres (its discs overlap by the hundred), far over the
+scene rule's mean of 64, so K renders from lists only under the test hook
+RT_TEST_OCC_MEAN (the K tests set it; one test checks that without it K
+reports occluder_lists_on == 0).  With the default cap of 32 about one K
+sphere in ten keeps a list, so list lanes and walk lanes mix inside its waves.
+"""
+import numpy as np
+import pytest
+
+import raytracingstudy_amd as rt
+from raytracingstudy_amd._lib import RtError
+from raytracingstudy_amd.camera import scene_pose
+
+pytestmark = pytest.mark.gpu
+
+U24 = 1.0 / 16777216.0
+EPS = float(np.float32(1e-5))      # kShadowEps
+WALK = 0xFFFFFFFF
+CAP = 32                           # kOccCap
+# the pair rule's slack (rt_params.h kOcc*, kShadowSlackM)
+REL, NORM_M, ABS_M, BEHIND_R, SELF_M, SLACK_M = 1e-4, 64.0, 128.0, 1.0, 48.0, 64.0
+CAM_GATE = 3.0                     # kOccCamGate
+LIGHT = (1.0, 1.0, -1.0)
+
+
+def _scene_u():
+    return rt.generate_spheres(3000, rt.SEED)
+
+
+def _scene_k():
+    n = 1500
+    rng = np.random.default_rng(20261019)
+    c = 0.64 + 0.03 * rng.normal(size=(n, 3))
+    r = 0.02 * (1000.0 / n) ** (1.0 / 3.0) * rng.uniform(0.5, 1.0, n)
+    sp = np.concatenate([c, r[:, None]], 1).astype(np.float32)
+    al = rng.integers(0x33, 0x100, size=(n, 3)).astype(np.uint32)
+    return sp, (al[:, 0] | (al[:, 1] << 8) | (al[:, 2] << 16) | np.uint32(0xFF000000)).astype(np.uint32)
+
+
+SCENES = {"U": _scene_u(), "K": _scene_k()}
+
+
+@pytest.fixture
+def hooks(monkeypatch):
+    """K on lists: the scene rule's mean lifted (a gated test hook)."""
+    def set_(name, cap=None):
+        if name == "K":
+            monkeypatch.setenv("RT_TEST_OCC_MEAN", "1e9")
+        if cap is not None:
+            monkeypatch.setenv("RT_TEST_OCC_CAP", str(cap))
+    return set_
+
+
+def _renderer(scene, w=96, h=64, spp=8, light=LIGHT, pose=None, **kw):
+    sp, al = SCENES[scene] if isinstance(scene, str) else scene
+    r = rt.KernelRenderer(w, h, mode="scene", spp=spp, radiance=True, light_dir=light, **kw)
+    r.resize(w, h)
+    r.setPosition(scene_pose() if pose is None else pose)
+    r.set_scene(sp, al)
+    return r
+
+
+def _kernel_light(ld):
+    """FrameArgs::L and the light-plane basis, as rt_capi.cpp makes them."""
+    ld = np.asarray(ld, np.float32)
+    ll = np.sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2], dtype=np.float32)
+    L = (-(ld / ll)).astype(np.float32)
+    l = L.astype(np.float64)
+    l /= np.linalg.norm(l)
+    k = int(np.argmin(np.abs(l)))      # first of the smallest, like the host loop
+    e1 = np.zeros(3)
+    e1[k] = 1.0
+    e1 -= l[k] * l
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(l, e1)
+    return L, e1.astype(np.float32).astype(np.float64), e2.astype(np.float32).astype(np.float64)
+
+
+def _rule(sp, info, ld, slack, shrink=1.0):
+    """The pair rule in f64: keep[i, j] iff j may occlude a shadow ray from i.
+    slack 0: exact discs r_i + 1e-5 and r_j; slack 1: the product's; 2: twice."""
+    L, e1, e2 = _kernel_light(ld)
+    c = sp[:, :3].astype(np.float64)
+    r = sp[:, 3].astype(np.float64) * shrink
+    corners = np.array([[(info["root_max"] if (k >> i) & 1 else info["root_min"])[i] for i in range(3)]
+                        for k in range(8)], np.float64)
+    M = np.linalg.norm(corners, axis=1).max() + 1e-4
+    delta = SLACK_M * U24 * M
+    u, v, w = c @ e1, c @ e2, c @ L.astype(np.float64)
+    R = r * (1 + REL) + EPS * (1 + NORM_M * U24 * M / r) + ABS_M * U24 * M
+    sr = (r * (1 + 4 * U24) + delta) * (1 + 4 * U24)
+    Ri = r + EPS + slack * (R - r - EPS)
+    srj = r + slack * (sr - r)
+    d2 = (u[:, None] - u[None]) ** 2 + (v[:, None] - v[None]) ** 2
+    keep = (d2 <= (Ri[:, None] + srj[None]) ** 2) & \
+           (w[None] + r[None] * (1 + slack * BEHIND_R) + Ri[:, None] + slack * delta >= w[:, None])
+    self_in = ~(SELF_M * U24 * (r + M) <= 0.75 * EPS)
+    keep[np.arange(len(r)), np.arange(len(r))] = self_in
+    return keep, (w - r)
+
+
+def _lists(r):
+    off, cnt, idx, refs = r.export_occluders()
+    return off, cnt, idx, refs
+
+
+# ---- 1. list contents ------------------------------------------------------
+
+@pytest.mark.parametrize("scene", ["U", "K"])
+def test_list_contents(gpu, hooks, scene):
+    hooks(scene)
+    sp, _ = SCENES[scene]
+    with _renderer(scene) as r:
+        r.render()
+        r.readback()   # a synchronisation: the build time is collected there
+        info = r.scene_info()
+        assert info["occluder_lists_on"] == 1 and info["occluder_build_ms"] > 0.0
+        off, cnt, idx, refs = _lists(r)
+        _, _, prim_idx = r.export_octree()
+    n = sp.shape[0]
+    lo, key = _rule(sp, info, LIGHT, 0.0)
+    hi, _ = _rule(sp, info, LIGHT, 2.0)
+    flagged = cnt == WALK
+    lens = np.where(flagged, 0, cnt).astype(np.int64)
+    # offsets and counts: the lists back to back in sphere order
+    assert np.array_equal(off.astype(np.int64), np.concatenate([[0], np.cumsum(lens)[:-1]]))
+    assert int(lens.sum()) == info["occluder_entries"] == idx.shape[0]
+    assert lens.max() <= CAP
+    # over the cap at zero slack: flagged; within it at twice the slack: a list
+    assert np.all(flagged[lo.sum(1) > CAP]) and not np.any(flagged[hi.sum(1) <= CAP])
+    assert (scene == "K") == bool(flagged.any())
+    n_lists = 0
+    for i in np.flatnonzero(~flagged):
+        li = idx[off[i]:off[i] + cnt[i]]
+        assert np.all(li < n)
+        member = np.zeros(n, bool)
+        member[li] = True
+        assert member.sum() == li.shape[0], f"sphere {i}: duplicates"
+        assert not np.any(lo[i] & ~member), f"sphere {i}: misses a rule pair"
+        assert not np.any(member & ~hi[i]), f"sphere {i}: holds a sphere outside twice the slack"
+        k = key[li]
+        order = (k[:-1] < k[1:]) | ((k[:-1] == k[1:]) & (li[:-1] < li[1:]))
+        assert np.all(order), f"sphere {i}: not sorted nearest-first"
+        n_lists += 1
+    assert n_lists >= 50
+    # every reference carries its sphere's header
+    assert refs.shape[0] == prim_idx.shape[0]
+    assert np.array_equal(refs[:, 0], off[prim_idx]) and np.array_equal(refs[:, 1], cnt[prim_idx])
+
+
+def test_two_builds_give_identical_arrays(gpu):
+    out = []
+    for _ in range(2):
+        with _renderer("U") as r:
+            r.render()
+            out.append(_lists(r))
+    for a, b in zip(*out):
+        assert np.array_equal(a, b)
+
+
+# ---- 2. soundness against the oracle ---------------------------------------
+
+def _shadow_rays(sp, L, n, rng):
+    """n shadow rays (origin p + 1e-5 n in f32, as the kernel forms it) from
+    points on lit hemispheres, n.L from 1e-7 to 1; half aimed at another
+    sphere's silhouette within 1e-7 .. 0.3 radii."""
+    Ld = L.astype(np.float64)
+    src = rng.integers(0, sp.shape[0], n)
+    c = sp[src, :3].astype(np.float64)
+    r = sp[src, 3].astype(np.float64)
+    ndl = 10.0 ** rng.uniform(-7, 0, n)
+    a = rng.normal(size=(n, 3))
+    t = a - (a @ Ld)[:, None] * Ld
+    t /= np.linalg.norm(t, axis=1)[:, None]
+    nrm = ndl[:, None] * Ld + np.sqrt(1 - ndl ** 2)[:, None] * t
+    aim = np.arange(n) % 2 == 0
+    # aimed: a neighbour j ahead along L; the point on i whose light-plane
+    # position is j's silhouette (when that lies inside i's disc)
+    e1 = np.cross(Ld, [1.0, 0.0, 0.0] if abs(Ld[0]) < 0.9 else [0.0, 1.0, 0.0])
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(Ld, e1)
+    uv = np.stack([sp[:, :3].astype(np.float64) @ e1, sp[:, :3].astype(np.float64) @ e2], 1)
+    wv = sp[:, :3].astype(np.float64) @ Ld
+    for k in np.flatnonzero(aim):
+        i = src[k]
+        d = np.linalg.norm(uv - uv[i], axis=1)
+        cand = np.flatnonzero((d < sp[i, 3] + sp[:, 3]) & (wv > wv[i]) & (np.arange(sp.shape[0]) != i))
+        if cand.size == 0:
+            continue
+        j = cand[rng.integers(cand.size)]
+        xi = 10.0 ** rng.uniform(-7, np.log10(0.3)) * rng.choice([-1.0, 1.0])
+        ang = rng.uniform(0, 2 * np.pi)
+        q = uv[j] + sp[j, 3] * (1 + xi) * np.array([np.cos(ang), np.sin(ang)]) - uv[i]
+        rho2 = q @ q / r[k] ** 2
+        if rho2 >= 1.0 - 1e-14:
+            continue
+        nl = np.sqrt(1.0 - rho2)  # n.L of the point above q on the lit side
+        nrm[k] = (q[0] * e1 + q[1] * e2) / r[k] + nl * Ld
+    p = (c + r[:, None] * nrm).astype(np.float32)
+    c32, r32 = sp[src, :3], sp[src, 3]
+    nn = ((p - c32) * (np.float32(1.0) / r32)[:, None]).astype(np.float32)
+    lit = (nn.astype(np.float64) @ Ld) > 0
+    o = (p + nn * np.float32(1e-5)).astype(np.float32)
+    return src[lit], o[lit]
+
+
+def _missing(s, sp, L, src, o, lists):
+    off, cnt, idx = lists
+    miss = found = 0
+    for i, oo in zip(src, o):
+        if cnt[i] == WALK:
+            continue
+        li = idx[off[i]:off[i] + cnt[i]]
+        for brute in (False, True):
+            h, _, j, _ = s.trace(oo, L, any_hit=True, brute=brute)
+            if h:
+                found += 1
+                miss += int(j not in li)
+    return miss, found
+
+
+@pytest.mark.parametrize("scene", ["U", "K"])
+def test_oracle_occluders_are_listed(gpu, oracle, hooks, scene):
+    hooks(scene, cap=64 if scene == "K" else None)
+    sp, al = SCENES[scene]
+    with _renderer(scene) as r:
+        r.render()
+        info = r.scene_info()
+        off, cnt, idx, _ = _lists(r)
+    L, _, _ = _kernel_light(LIGHT)
+    rng = np.random.default_rng(7)
+    src, o = _shadow_rays(sp, L, 20000, rng)
+    assert src.shape[0] > 15000
+    s = oracle.Scene(sp, al)
+    miss, found = _missing(s, sp, L, src, o, (off, cnt, idx))
+    assert found > 1000 and miss == 0, f"{miss} of {found} occluders not in the source sphere's list"
+    # negative control: lists from the rule with every radius x 0.9 miss some
+    keep, _ = _rule(sp, info, LIGHT, 1.0, shrink=0.9)
+    lens = keep.sum(1)
+    off9 = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint32)
+    idx9 = np.nonzero(keep)[1].astype(np.uint32)
+    cnt9 = np.where(cnt == WALK, WALK, lens).astype(np.uint32)
+    miss9, _ = _missing(s, sp, L, src, o, (off9, cnt9, idx9))
+    assert miss9 > 0, "the check cannot see an unsound list"
+    s.close()
+
+
+# ---- 3. frames -------------------------------------------------------------
+
+def _check_frames(r, s, w, h, spp, light=LIGHT):
+    """plain (lists) == stats (walk) == oracle, RGBA8 and radiance; counters."""
+    pose_k, K = r.camera()
+    r.render()
+    img, rad = r.readback(), r.readback_radiance()
+    st = r.render(stats=True)
+    ref8, ref32, cnt = s.render(w, h, pose_k, K, spp=spp, light_dir=light)
+    assert np.array_equal(img, r.readback()) and np.array_equal(rad, r.readback_radiance())
+    assert np.array_equal(img, ref8) and np.array_equal(rad, ref32)
+    assert (st.primary_rays, st.shadow_rays, st.nodes_visited, st.prims_tested) == tuple(int(c) for c in cnt)
+    assert int(cnt[1]) > 0   # the frame casts shadow rays
+    return img, rad
+
+
+@pytest.fixture(scope="module")
+def oracle_scenes(oracle):
+    ss = {k: oracle.Scene(*v) for k, v in SCENES.items()}
+    yield ss
+    for s in ss.values():
+        s.close()
+
+
+@pytest.mark.parametrize("scene,w,h,spp,cap", [
+    ("U", 96, 64, 8, None), ("K", 96, 64, 8, None), ("U", 64, 48, 1, None),
+    ("U", 32, 24, 256, None),   # the sorted path
+    ("K", 96, 64, 8, 2),        # nearly every K sphere walks: list and walk lanes in one wave
+    ("K", 32, 24, 256, None),
+])
+def test_frames_match_walk_and_oracle(gpu, hooks, oracle_scenes, scene, w, h, spp, cap):
+    hooks(scene, cap)
+    with _renderer(scene, w, h, spp) as r:
+        img, rad = _check_frames(r, oracle_scenes[scene], w, h, spp)
+        assert r.scene_info()["occluder_lists_on"] == 1
+    with _renderer(scene, w, h, spp, occluders=False) as r:   # the A/B switch: identical bytes
+        r.render()
+        assert r.scene_info()["occluder_lists_on"] == 0
+        assert np.array_equal(r.readback(), img) and np.array_equal(r.readback_radiance(), rad)
+
+
+@pytest.mark.parametrize("light", [(1.0, 1.0, -1.0), (0.0, 0.0, -1.0), (1.0, 0.01, 0.0)])
+def test_light_directions(gpu, oracle_scenes, light):
+    with _renderer("U", light=light) as r:
+        _check_frames(r, oracle_scenes["U"], 96, 64, 8, light=light)
+        assert r.scene_info()["occluder_lists_on"] == 1
+
+
+def test_camera_inside_a_sphere(gpu, oracle_scenes):
+    sp, _ = SCENES["U"]
+    pose = np.array(scene_pose(), np.float32).reshape(4, 4).copy()
+    pose[3, :3] = sp[11, :3] + np.float32(0.3) * sp[11, 3]
+    with _renderer("U", pose=pose) as r:
+        _check_frames(r, oracle_scenes["U"], 96, 64, 8)
+
+
+def _cam_ratio(pose, info):
+    """(|o_cam| + the camera's distance to the root box's farthest corner) / M,
+    the quantity the per-frame gate compares with kOccCamGate."""
+    o = np.asarray(pose, np.float64).reshape(4, 4)[3, :3]
+    lo, hi = np.asarray(info["root_min"], np.float64), np.asarray(info["root_max"], np.float64)
+    far = np.linalg.norm(np.maximum(np.abs(o - lo), np.abs(o - hi)))
+    corners = np.array([[(hi if (k >> i) & 1 else lo)[i] for i in range(3)] for k in range(8)])
+    return (np.linalg.norm(o) + far) / (np.linalg.norm(corners, axis=1).max() + 1e-4)
+
+
+@pytest.mark.parametrize("scene,z", [("U", 3.0), ("U", 300.0), ("U", 3000.0), ("K", 300.0), ("K", 3000.0)])
+def test_far_camera(gpu, hooks, oracle_scenes, scene, z):
+    """The hit point's rounding grows with the camera's distance, and the
+    lists' bounds hold it only inside the gate: z = 3.0 is inside it (lists),
+    z = 300 and 3000 are far outside, where hundreds of shadow origins land
+    inside their own sphere and the walk reports them shadowed; those frames
+    must walk.  A long focal length keeps the scene filling the frame."""
+    hooks(scene)
+    w, h, spp = 96, 64, 8
+    pose = np.array(scene_pose(), np.float32).reshape(4, 4).copy()
+    pose[3, 2] = z
+    with _renderer(scene, w, h, spp, pose=pose) as r:
+        _, K = r.camera()
+        K = np.array(K, np.float32).copy()
+        zoom = (z - 0.64) / (2.2 - 0.64) * (8.0 if scene == "K" else 1.0)
+        K[0, 0] *= zoom
+        K[1, 1] *= zoom
+        r.setIntrinsic(K)
+        _check_frames(r, oracle_scenes[scene], w, h, spp)
+        info = r.scene_info()
+        assert info["occluder_lists_on"] == 1
+        assert (_cam_ratio(pose, info) <= CAM_GATE) == (z == 3.0)
+
+
+def test_tiles_match_whole_frame(gpu):
+    import torch
+    w, h, ts = 96, 64, 64
+    ids = np.arange(((w + ts - 1) // ts) * ((h + ts - 1) // ts), dtype=np.uint32)
+    with _renderer("U") as full, _renderer("U") as tiled:
+        packed = torch.zeros(len(ids) * ts * ts * 4, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        full.render()
+        tiled.render_tiles(ids, ts, packed.data_ptr())
+        tiled.unpack_tiles(packed.data_ptr(), ids, ts)
+        assert tiled.scene_info()["occluder_lists_on"] == 1
+        assert np.array_equal(tiled.readback(), full.readback())
+
+
+def test_progressive_second_frame(gpu, oracle_scenes):
+    w, h, spp = 96, 64, 8
+    acc = np.zeros((h, w, 4), np.float32)
+    with _renderer("U", progressive=True) as r:
+        pose, K = r.camera()
+        for k in range(2):
+            r.render()   # plain frames: the lists
+            img, rad, _ = oracle_scenes["U"].render(w, h, pose, K, spp=spp, frame=k, accum=acc)
+            assert np.array_equal(r.readback(), img), k
+            assert np.array_equal(r.readback_radiance(), rad), k
+
+
+# ---- 4. scene rule ---------------------------------------------------------
+
+def test_dense_scene_walks(gpu, oracle_scenes):
+    """K without the hook: its mean candidate count is over the rule's, so it
+    gets no lists and its frames are the walk's."""
+    with _renderer("K") as r:
+        _check_frames(r, oracle_scenes["K"], 96, 64, 8)
+        info = r.scene_info()
+        assert info["occluder_lists_on"] == 0 and info["occluder_entries"] == 0
+        with pytest.raises(RtError):
+            r.export_occluders()
+
+
+@pytest.mark.parametrize("bad", ["nan_radius", "zero_radius"])
+def test_invalid_sphere_never_reaches_the_lists(gpu, bad):
+    """A scene with a NaN or zero radius is refused by set_scene (as before
+    this change), so no frame can meet lists built over one: the renderer
+    keeps its previous scene, lists and frames.  (The builder also counts
+    such spheres and gives the scene no lists, which no API path reaches.)"""
+    sp, al = SCENES["U"]
+    badsp = sp.copy()
+    badsp[5, 3] = np.nan if bad == "nan_radius" else 0.0
+    with _renderer("U") as r, _renderer("U", occluders=False) as off:
+        r.render()
+        off.render()
+        want = off.readback()
+        assert np.array_equal(r.readback(), want)
+        with pytest.raises(RtError):
+            r.set_scene(badsp, al)
+        r.render()
+        assert r.scene_info()["occluder_lists_on"] == 1
+        assert np.array_equal(r.readback(), want)
+
+
+# ---- 5. scene change -------------------------------------------------------
+
+def test_scene_change_rebuilds_the_lists(gpu, hooks, oracle_scenes):
+    hooks("K")
+    with _renderer("U") as r:
+        r.render()
+        u_lists = _lists(r)
+        r.set_scene(*SCENES["K"])
+        _check_frames(r, oracle_scenes["K"], 96, 64, 8)
+        k_lists = _lists(r)
+    assert k_lists[0].shape[0] == SCENES["K"][0].shape[0] != u_lists[0].shape[0]
+    with _renderer("K") as fresh:
+        fresh.render()
+        for a, b in zip(k_lists, _lists(fresh)):
+            assert np.array_equal(a, b)

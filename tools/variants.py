@@ -31,9 +31,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--spp", type=int, default=0, help="override spp")
     args = ap.parse_args()
-    # a variant spec is "V", "V:OPT", "V:OPT:T" or "V:OPT:T:CAP" (OPT = rt_config
-    # opt bits, A/B toggles; T = cell-table depth: 0 off, 1..7, absent = chosen
-    # from the tree; CAP = octree leaf capacity, absent = the config's)
+    # a variant spec is "V", "V:OPT", "V:OPT:T", "V:OPT:T:CAP" or "V:OPT:T:CAP:OCC"
+    # (OPT = rt_config opt bits, A/B toggles; T = cell-table depth: 0 off, 1..7,
+    # absent = chosen from the tree; CAP = octree leaf capacity, absent = the
+    # config's; OCC = 0: no occluder lists, every shadow ray walks)
     variants = args.variants.split(",")
     if len(set(variants)) != len(variants):
         ap.error("--variants: each spec at most once (rounds repeat them)")
@@ -46,15 +47,19 @@ def main():
         for v in variants:
             vv, _, rest = v.partition(":")
             oo, _, rest = rest.partition(":")
-            tt, _, cc = rest.partition(":")
+            tt, _, rest = rest.partition(":")
+            cc, _, occ = rest.partition(":")
             r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=spp, variant=int(vv),
-                                  opt_off=int(oo or 0), cell_table=int(tt) if tt else None)
+                                  opt_off=int(oo or 0), cell_table=int(tt) if tt else None,
+                                  occluders=occ != "0")
             r.resize(cfg.width, cfg.height)
             r.setPosition(scene_pose())
             info = r.set_scene(sp, al, max_depth=cfg.max_depth,
                                leaf_capacity=int(cc) if cc else cfg.leaf_capacity)
             r.cell_table_depth = info["cell_table_depth"]
             r.render(stats=True)  # warm-up
+            r.occ = {k: v for k, v in r.scene_info().items() if k.startswith("occluder_")}
+            r.scene_build_ms = info["build_ms"]
             rs[v] = r
         # timed frames are plain frames (no work counters), HIP events on a torch stream
         import torch
@@ -82,6 +87,8 @@ def main():
                       "nodes_per_ray": round(st.nodes_visited / rays, 2),
                       "prims_per_ray": round(st.prims_tested / rays, 2),
                       "cell_table_depth": rs[v].cell_table_depth,
+                      "scene_build_ms": round(rs[v].scene_build_ms, 3),
+                      **{k: round(x, 3) if isinstance(x, float) else x for k, x in rs[v].occ.items()},
                       # across libraries (tools/ab_libs.sh): equal images, equal hashes
                       "image_sha1": __import__("hashlib").sha1(img.tobytes()).hexdigest()[:12],
                       "counters": [int(st.primary_rays), int(st.shadow_rays), int(st.nodes_visited),
