@@ -101,8 +101,10 @@ enum {
      * covering the root box.  Images and counters are the same for all three. */
     RT_FLAG_PAD_FILL_SHIFT = 8,
     /* Test-only: rt_create / rt_create_multi honour the RT_TEST_* environment
-     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY, RT_TEST_OCC_CAP, RT_TEST_OCC_MEAN); without
-     * this flag they are ignored (a set one is named on stderr once). */
+     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY, RT_TEST_OCC_CAP, RT_TEST_OCC_MEAN)
+     * and the A/B switches RT_SORT, RT_LDS_STAGE, RT_LEAF_PACK and RT_SB_ORDER
+     * (none changes an image); without this flag they are
+     * ignored (a set one is named on stderr once). */
     RT_FLAG_TEST_HOOKS = 1u << 10,
     /* Test-only: before every frame, fill the frame's outputs with a sentinel
      * (RGBA8 bytes 0xAB, frame or packed tiles; radiance and a first

@@ -599,8 +599,10 @@ void orc_cam8_screen_check(const float o[3], const float B[9], uint32_t ok, cons
 }
 
 /* Test-only: the light-plane screen with 8-byte records carrying each
- * sphere's own rr' as bf16 in the low bytes of {u, v} (rt_kernels.hip
- * shd_screen_kernel and walk<> under RT_SHD8_PER): as orc_shd_screen_check,
+ * sphere's own rr' as bf16 in the low bytes of {u, v} (the RT_SHD8_PER arm
+ * of shd_screen_kernel and walk<>, measured slower and removed from the
+ * kernels in round 8; this model stays as the record of its soundness): as
+ * orc_shd_screen_check,
  * the radius grown by the stored centre's error 2^-14 (|u| + |v|) and the
  * result scaled by shrink (1 = the product). */
 void orc_shd8_screen_check(const float* origins, const float L[3], const float* sp,

@@ -27,7 +27,7 @@
 
 namespace rtamd {
 hipError_t launch_compat(const FrameArgs& a, hipStream_t st);
-hipError_t launch_scene(const FrameArgs& a, hipStream_t st);
+hipError_t launch_scene(const FrameArgs& a, bool sort, hipStream_t st);
 bool variant_available(uint32_t v);
 hipError_t launch_unpack(const uint32_t* packed, const uint32_t* tiles, uint32_t n_tiles,
                          uint32_t ts, uint32_t tiles_x, uint32_t W, uint32_t H, uint32_t* img,
@@ -35,7 +35,7 @@ hipError_t launch_unpack(const uint32_t* packed, const uint32_t* tiles, uint32_t
 hipError_t launch_cam_screen(const float4* prim_sp, uint32_t n, const float o[3], float4* out,
                              hipStream_t st);
 hipError_t launch_shd_screen(const float4* prim_sp, uint32_t n, const float e[6], double delta,
-                             float4* out, float2* out8, uint32_t* rr_max, hipStream_t st);
+                             float2* out8, uint32_t* rr_max, hipStream_t st);
 hipError_t launch_albedo_refs(const uint32_t* prim_idx, const uint32_t* albedo, uint32_t n,
                               uint32_t n_spheres, uint32_t* out, hipStream_t st);
 hipError_t launch_cam8_screen(const float4* prim_sp, uint32_t n, const float o[3], const float B[9],
@@ -183,6 +183,11 @@ struct rt_renderer {
     // test only: RT_TEST_CLAIM_DELAY at rt_create with RT_FLAG_TEST_HOOKS
     // (FrameArgs::wq_claim_delay)
     uint32_t test_claim_delay = 0;
+    // test only, read at rt_create with RT_FLAG_TEST_HOOKS: the A/B switches
+    // RT_SORT=0 (no sorted rounds), RT_LDS_STAGE=0 (no LDS leaf staging),
+    // RT_LEAF_PACK=1 (line-packed leaf lists) and RT_SB_ORDER=1 (superblocks
+    // claimed along a Hilbert curve); images and counters are the same
+    bool sort_rounds = true, lds_stage = true, leaf_pack = false, sb_hilbert = false;
     rt_octree_params oct;
     bool has_scene = false;
     GpuOctreeBuilder gpu_build;
@@ -197,14 +202,12 @@ struct rt_renderer {
     // made for: the scene build and the camera origin
     DevBuf<float4> d_prim_cam;
     uint64_t scene_gen = 0, cam_gen = ~0ull;
-    // light-plane screen records (SceneArgs::prim_shd) and the basis and
-    // scene they were made for
-    DevBuf<float4> d_prim_shd;
+    // the basis and the scene the light-plane screen records were made for
     uint64_t shd_gen = ~0ull;
     float shd_e[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float cam_o[3] = {0.f, 0.f, 0.f};
-    // the light-plane records in 8 bytes (SceneArgs::prim_shd8) and their
-    // radius term (FrameArgs::shd_rr; rr_dev: the kernel's max, in bits)
+    // the light-plane screen records, {u, v} in 8 bytes (SceneArgs::prim_shd8),
+    // and their radius term (FrameArgs::shd_rr; rr_dev: the kernel's max, in bits)
     DevBuf<float2> d_prim_shd8;
     DevBuf<uint32_t> d_shd_rr;
     float shd_rr = 0.0f;
@@ -371,15 +374,6 @@ void fill_frame_args(rt_renderer* r, FrameArgs& a) {
     a.variant = v ? v : (a.spp >= 8u ? kVariantWaveQ : kVariantWaveQLow);
 }
 
-// An A/B switch read from the environment ("0" off, anything else on), or dflt.
-bool env_flag(const char* name, bool dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) != 0 : dflt;
-}
-#ifndef RT_LEAF_PACK_DEFAULT
-#define RT_LEAF_PACK_DEFAULT 0
-#endif
-
 // A test hook's environment variable (RT_TEST_*): its value when the config
 // carries RT_FLAG_TEST_HOOKS, else NULL.  Either way a set variable is named
 // on stderr once per process, so a stray one is visible.
@@ -433,10 +427,6 @@ std::vector<uint32_t> hilbert_order(uint32_t nx, uint32_t ny) {
     }
     return out;
 }
-#ifndef RT_SB_ORDER_DEFAULT
-#define RT_SB_ORDER_DEFAULT 0
-#endif
-
 // Leaf records of a breadth-first tree: a record's kind is in
 // its parent's leaf mask, and children come after their parent, so one
 // forward pass over the records finds them all.  Returned in record order.
@@ -646,11 +636,11 @@ int build_scene(rt_renderer* r) {
         }
         float4 pad[kPrimPad];
         for (uint32_t i = 0; i < kPrimPad; ++i) pad[i] = p1;
-        // the line-packed layout's gaps hold the same (RT_LEAF_PACK=1, an A/B
-        // switch read here; off by default: measured no faster)
+        // the line-packed layout's gaps hold the same (RT_LEAF_PACK=1, a test
+        // hook; off by default: measured no faster)
         r->prim_slots = in.n_prim_refs;
         r->leaf_packed = false;
-        if (!sc.root_is_leaf && env_flag("RT_LEAF_PACK", RT_LEAF_PACK_DEFAULT) &&
+        if (!sc.root_is_leaf && r->leaf_pack &&
             (st = pack_leaf_lines(r, sc, in, p1)))
             return st;
         float4* tail = const_cast<float4*>(sc.prim_sp) + r->prim_slots;
@@ -673,12 +663,9 @@ int build_scene(rt_renderer* r) {
     sc.albedo = r->d_albedo.p;
     sc.max_depth = depth;
     sc.stack_depth = std::max(1u, std::min(depth, in.depth_reached));
-    {
-        // LDS leaf staging on every scene; RT_LDS_STAGE=0
-        // turns it off (A/B and the on/off parity test)
-        const char* ls = getenv("RT_LDS_STAGE");
-        sc.lds_max = ls && *ls && atoi(ls) == 0 ? 0u : kLeafBuf;
-    }
+    // LDS leaf staging on every scene; RT_LDS_STAGE=0, a test
+    // hook, turns it off (the on/off parity test)
+    sc.lds_max = r->lds_stage ? kLeafBuf : 0u;
     sc.G = static_cast<float>(1u << depth);
     for (int i = 0; i < 3; ++i) {
         sc.rmin[i] = rmin[i];
@@ -916,8 +903,7 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
         RT_HIP(r, hipMemsetAsync(ctr, 0, words * sizeof(unsigned long long), st));
     if (a.wq_slot_stride) a.wq_slots = reinterpret_cast<uint32_t*>(ctr + kCounterWords);
     a.sb_order = nullptr;
-    if (r->cfg.mode == RT_MODE_SCENE && !a.tiles && a.wq_slot_shift == 12u &&
-        env_flag("RT_SB_ORDER", RT_SB_ORDER_DEFAULT)) {
+    if (r->cfg.mode == RT_MODE_SCENE && !a.tiles && a.wq_slot_shift == 12u && r->sb_hilbert) {
         // the superblock grid of this frame (scene_body's nsx x nsy)
         uint32_t spw, g, ppw, tw, th;
         wave_tile_shape(a.spp, spw, g, ppw, tw, th);
@@ -989,13 +975,11 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
             a.shd_e[i] = static_cast<float>(e1[i]);
             a.shd_e[3 + i] = static_cast<float>(e2[i]);
         }
-        const float4* before_s = r->d_prim_shd.p;
         const float2* before_s8 = r->d_prim_shd8.p;
-        if ((ost = ensure(r, r->d_prim_shd, nr))) return ost;
         if ((ost = ensure(r, r->d_prim_shd8, nr))) return ost;
         const uint32_t nbk = (nr + kBlockThreads - 1u) / kBlockThreads;  // shd_screen_kernel's blocks
         if ((ost = ensure(r, r->d_shd_rr, nbk + 1u))) return ost;
-        if (r->d_prim_shd.p != before_s || r->d_prim_shd8.p != before_s8 || r->shd_gen != r->scene_gen ||
+        if (r->d_prim_shd8.p != before_s8 || r->shd_gen != r->scene_gen ||
             memcmp(r->shd_e, a.shd_e, sizeof(r->shd_e)) != 0) {
             // M bounds |origin| and |centre| of every shadow test: the root
             // box holds every sphere, and a shadow origin is a hit point
@@ -1011,8 +995,8 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
             }
             const double delta = kShadowSlackM / 16777216.0 * (m + 1e-4);
             RT_HIP(r, hipMemsetAsync(r->d_shd_rr.p, 0, (nbk + 1u) * sizeof(uint32_t), st));
-            hipError_t e = launch_shd_screen(a.sc.prim_sp, nr, a.shd_e, delta, r->d_prim_shd.p,
-                                             r->d_prim_shd8.p, r->d_shd_rr.p, st);
+            hipError_t e = launch_shd_screen(a.sc.prim_sp, nr, a.shd_e, delta, r->d_prim_shd8.p,
+                                             r->d_shd_rr.p, st);
             if (e != hipSuccess) return hip_fail(r, e, "light-plane screen records");
             // the 8-byte records' radius term, once per scene and light (a sync)
             uint32_t bits = 0;
@@ -1050,7 +1034,6 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
             memcpy(r->shd_e, a.shd_e, sizeof(r->shd_e));
             r->shd_gen = r->scene_gen;
         }
-        a.sc.prim_shd = r->d_prim_shd.p;
         a.sc.prim_shd8 = r->d_prim_shd8.p;
         a.shd_rr = r->shd_rr;
         a.sc.prim_occ = r->occ.prim_occ();
@@ -1109,7 +1092,7 @@ int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats) {
         a.bstats = bsd;
     }
 #endif
-    hipError_t e = r->cfg.mode == RT_MODE_SCENE ? launch_scene(a, st) : launch_compat(a, st);
+    hipError_t e = r->cfg.mode == RT_MODE_SCENE ? launch_scene(a, r->sort_rounds, st) : launch_compat(a, st);
     if (e != hipSuccess) {
         r->ctr_zero[0] = r->ctr_zero[1] = 0;  // neither set is known to be zero
         return hip_fail(r, e, "kernel launch");
@@ -1254,6 +1237,11 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
     if (const char* om = test_env(cfg->flags, "RT_TEST_OCC_MEAN")) r->occ_mean_max = strtod(om, nullptr);
     if (const char* fe = test_env(cfg->flags, "RT_TEST_FAULT"))
         r->test_fault_queue = strcmp(fe, "queue:0") == 0;
+    // ... and the A/B switches ("0" off, any other number on)
+    if (const char* v = test_env(cfg->flags, "RT_SORT")) r->sort_rounds = atoi(v) != 0;
+    if (const char* v = test_env(cfg->flags, "RT_LDS_STAGE")) r->lds_stage = atoi(v) != 0;
+    if (const char* v = test_env(cfg->flags, "RT_LEAF_PACK")) r->leaf_pack = atoi(v) != 0;
+    if (const char* v = test_env(cfg->flags, "RT_SB_ORDER")) r->sb_hilbert = atoi(v) != 0;
     // src/renderer.cu:87-89: K0 = mat3(1000,0,640, 0,1000,340, 0,0,1), pose = mat4(1)
     const float K0[9] = {1000.f, 0.f, 640.f, 0.f, 1000.f, 340.f, 0.f, 0.f, 1.f};
     memcpy(r->K, K0, sizeof(K0));
@@ -1325,7 +1313,6 @@ int rt_destroy(rt_renderer* r) {
     r->d_prim_cam8.release();
     r->d_prim_shd8.release();
     r->d_shd_rr.release();
-    r->d_prim_shd.release();
     r->q_counters.release();
     r->q_ray.release();
     r->q_hit.release();

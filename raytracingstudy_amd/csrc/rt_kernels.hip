@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -184,16 +183,16 @@ __device__ __forceinline__ void flush_counters(const FrameArgs& a, uint32_t prim
     }
 }
 
-// The hit record a nearest walk returned (`iout`: a leaf reference under
-// RT_REF_SHADE, else a sphere index): its sphere and its packed albedo.
+// The hit record a nearest walk returned (`iout`, a leaf reference): its
+// sphere and its packed albedo.
 // (SA: SceneArgs, or the kernel arguments' copy behind kernargs())
 template <typename SA>
 __device__ __forceinline__ float4 hit_sphere_rec(SA& S, uint32_t h) {
-    return RT_REF_SHADE ? S.prim_sp[h] : S.spheres[h];
+    return S.prim_sp[h];
 }
 template <typename SA>
 __device__ __forceinline__ uint32_t hit_albedo(SA& S, uint32_t h) {
-    return RT_REF_SHADE ? S.prim_al[h] : S.albedo[h];
+    return S.prim_al[h];
 }
 
 // Unified lane path: one walk instance run twice (primary, then the shadow ray
@@ -203,8 +202,7 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                                                          uint32_t y, uint32_t hp, uint32_t s,
                                                          bool valid, uint32_t& n_shadow,
                                                          uint32_t& n_nodes, uint32_t& n_prims,
-                                                         void* stk, uint32_t* bs = nullptr,
-                                                         uint32_t lbs = ~0u) {
+                                                         void* stk, uint32_t* bs, uint32_t lbs) {
     const SceneArgs& S = a.sc;
     KernArgs* ka = kernargs();
     float u = static_cast<float>(x), v = static_cast<float>(y);
@@ -241,15 +239,17 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                                                          static_cast<uint2*>(stk), false, bs, lbs);
             else if (kOcc) {
                 // answered from the hit sphere's occluder list (round 7)
-                hit = shadow_occluded<false>(S, occ_hdr, true, r0, r1, r2, static_cast<uint2*>(stk), lbs);
+                hit = shadow_occluded<false>(S, occ_hdr, true, r0, r1, r2, static_cast<uint2*>(stk));
             } else {
                 // the shadow direction L is the frame's, the same in every
                 // lane: read afresh from the kernel arguments (SGPRs), not the
                 // lanes' d registers
                 KernArgs* kl = kernargs();
-                hit = walk<true, RT_SHD_CHUNK, false, kStats, false, true>(
+                // (2 spheres a chunk, one dwordx4 of 8-byte records: 4 spills
+                // 48-100 B, C3 +6%, C5 +8%, C5d +5%, profiles/r06/ab_shd_chunk4.log)
+                hit = walk<true, 2, false, kStats, false, true>(
                     S, r0, r1, r2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, t, idx, n_nodes,
-                    n_prims, static_cast<uint2*>(stk), true, bs, lbs);
+                    n_prims, static_cast<uint2*>(stk), true, bs);
             }
         }
         if (phase == 0) {
@@ -308,8 +308,7 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
                                                 uint32_t ox, uint32_t oy, uint32_t obase,
                                                 uint32_t& n_primary,
                                                 uint32_t& n_shadow, uint32_t& n_nodes,
-                                                uint32_t& n_prims, uint32_t* bs = nullptr,
-                                                uint32_t lbs = ~0u) {
+                                                uint32_t& n_prims, uint32_t* bs, uint32_t lbs) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t spw = a.spw, g = a.g;
     const uint32_t pix = lane / g, sub = lane & (g - 1u);
@@ -450,7 +449,7 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
                                                    uint32_t x, uint32_t y, uint32_t obase,
                                                    uint32_t& n_primary, uint32_t& n_shadow,
                                                    uint32_t& n_nodes, uint32_t& n_prims,
-                                                   uint32_t* bs, uint32_t lbs) {
+                                                   uint32_t* bs) {
     const SceneArgs& S = a.sc;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t R = a.rounds;
@@ -509,10 +508,9 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         if (valid) {
             RT_BS(kBsPhase);
             KernArgs* kc = kernargs();
-            hit = walk<false, kChunk, true, kStats, true, false, RT_CAM8_SORTED != 0>(S, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2],
+            hit = walk<false, kChunk, true, kStats, true, false, true>(S, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2],
                                                           d0, d1, d2, 0.0f, INFINITY, t, idx, n_nodes,
-                                                          n_prims, static_cast<uint2*>(stk), false, bs,
-                                                          lbs);
+                                                          n_prims, static_cast<uint2*>(stk), false, bs);
         }
         bool is_lit = false;
         if (valid) {
@@ -562,16 +560,16 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         bool occ = false;
         if (kOcc) {
             // answered from the hit spheres' occluder lists (round 7)
-            occ = shadow_occluded<true>(S, occ_hdr, has, o0, o1, o2, static_cast<uint2*>(stk), lbs);
+            occ = shadow_occluded<true>(S, occ_hdr, has, o0, o1, o2, static_cast<uint2*>(stk));
         } else if (has) {
             RT_BS(kBsPhase);
             RT_BS(kBsPhaseShadow);
             KernArgs* kl = kernargs();
             float ts;
             uint32_t is;
-            occ = walk<false, RT_SHD_CHUNK, true, kStats, true, true>(
+            occ = walk<false, 2, true, kStats, true, true>(
                 S, o0, o1, o2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, ts, is, n_nodes,
-                n_prims, static_cast<uint2*>(stk), true, bs, lbs);
+                n_prims, static_cast<uint2*>(stk), true, bs);
         }
         if (has) {
             RT_BS(kBsShadeLoad);
@@ -676,11 +674,8 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
     // threadIdx inside the walk it lived in a VGPR, which the sorted 64-VGPR
     // build spilled to scratch and reloaded (a scratch load and a vmcnt(0)
     // wait) on every staged leaf.  C5 -1.2%, C5d -0.3% (sorted), C3 -0.4%
-    // (profiles/r06/ab_leaf_base_*.log); RT_LB_SGPR=0: as before
-#ifndef RT_LB_SGPR
-#define RT_LB_SGPR 1
-#endif
-    const uint32_t lbs = RT_LB_SGPR ? __builtin_amdgcn_readfirstlane(leaf_buf_base(a.sc, kSort)) : ~0u;
+    // (profiles/r06/ab_leaf_base_*.log)
+    const uint32_t lbs = __builtin_amdgcn_readfirstlane(leaf_buf_base(a.sc, kSort));
     // the next frame's counters, queue heads and slot table (the other set,
     // FrameArgs::ctr_next): zeroed here by the first workgroup, so frames run
     // back to back with no memset launch between them.  The previous frame,
@@ -859,9 +854,9 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
 #endif
                 if (kSort)
                     shade_pixel_sorted<kTiles, kChunk, kStats, kProg, kOcc>(
-                        a, wl, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs, lbs);
+                        a, wl, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs);
                 else
-                    shade_wave_tile<kTiles, kChunk, kStats, kProg, RT_CAM8 != 0 && !kSort, kOcc>(
+                    shade_wave_tile<kTiles, kChunk, kStats, kProg, !kSort, kOcc>(
                         a, acc, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs, lbs);
 #ifdef RT_TIMELINE
                 // per unit {start, end, hw_id << 32 | xcc << 16 | wave index}
@@ -986,17 +981,18 @@ __global__ void __launch_bounds__(kBlockThreads)
     const double rr = static_cast<double>(c.w) * c.w;
     const double u = 1.0 / 16777216.0;  // 2^-24, the f32 unit roundoff
     const double cd = oo - rr - (kScreenSlackOc * u) * oo - (kScreenSlackR * u) * rr;
-    out[i] = make_float4(x, y, z, kCamMode == 2 ? c.w : __double2float_rd(cd));
+    out[i] = make_float4(x, y, z, __double2float_rd(cd));
 }
 
-// Light-plane screen records (SceneArgs::prim_shd): per
-// reference the centre's {u, v} = {c.e1, c.e2} (f64, rounded to nearest) and
-// rr' = ((r (1 + 4u) + delta)^2 (1 + 4u)) rounded up, delta = the slack for
-// this scene (kShadowSlackM u M).  One thread per reference.
+// Light-plane screen records (SceneArgs::prim_shd8): per
+// reference the centre's {u, v} = {c.e1, c.e2} (f64, rounded to nearest); the
+// radius term is the largest rr' = ((r (1 + 4u) + delta)^2 (1 + 4u)) rounded
+// up, delta = the slack for this scene (kShadowSlackM u M).  One thread per
+// reference.
 __global__ void __launch_bounds__(kBlockThreads)
     shd_screen_kernel(const float4* __restrict__ prim_sp, uint32_t n, float e0, float e1, float e2,
-                      float e3, float e4, float e5, double delta, float4* __restrict__ out,
-                      float2* __restrict__ out8, uint32_t* __restrict__ rr_max) {
+                      float e3, float e4, float e5, double delta, float2* __restrict__ out8,
+                      uint32_t* __restrict__ rr_max) {
     const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
     uint32_t rb = 0u;
     if (i < n) {
@@ -1006,42 +1002,22 @@ __global__ void __launch_bounds__(kBlockThreads)
         const double ur = 1.0 / 16777216.0;
         const double rg = static_cast<double>(c.w) * (1.0 + 4.0 * ur) + delta;
         const float rr = __double2float_ru(rg * rg * (1.0 + 4.0 * ur));
-        out[i] = make_float4(static_cast<float>(u), static_cast<float>(v), rr, 0.0f);
-        if (out8) {
-            const float uf = static_cast<float>(u), vf = static_cast<float>(v);
-            if (RT_SHD8_PER) {
-                // this sphere's rr', grown by the stored centre's error (its
-                // 8 low mantissa bits a coordinate carry rr': <= 2^-15 |u|
-                // each), rounded up to bf16 (its soundness test: tests/test_cam_screen.py)
-                const double ec = (1.0 / 16384.0) * (fabs(static_cast<double>(uf)) + fabs(static_cast<double>(vf)));
-                const double rg8 = rg + ec;
-                const float r8 = __double2float_ru(rg8 * rg8 * (1.0 + 4.0 * ur));
-                uint32_t b8 = __float_as_uint(r8);
-                if (b8 & 0xFFFFu) b8 = (b8 & 0xFFFF0000u) + 0x10000u;
-                if (!(isfinite(r8) && b8 < 0x7F800000u)) b8 = 0x7F800000u;  // always pass
-                out8[i] = make_float2(__uint_as_float((__float_as_uint(uf) & ~0xFFu) | (b8 >> 24)),
-                                      __uint_as_float((__float_as_uint(vf) & ~0xFFu) | ((b8 >> 16) & 0xFFu)));
-            } else {
-                out8[i] = make_float2(uf, vf);
-            }
-        }
+        out8[i] = make_float2(static_cast<float>(u), static_cast<float>(v));
         rb = __float_as_uint(rr);
     }
-    if (out8) {
-        // the largest rr' (non-negative floats order as their bits; a NaN
-        // radius, the test-only pad fill, orders above every number): the
-        // block's maximum into rr_max[blockIdx.x], reduced by
-        // max_bits_kernel (atomics on one word serialise across the XCDs:
-        // one per record, or one per wave, took C5d's 4.9 M records 0.87 ms)
-        __shared__ uint32_t wmax[kBlockThreads / 64];
-        for (int d = 32; d > 0; d >>= 1) rb = max(rb, static_cast<uint32_t>(__shfl_xor(static_cast<int>(rb), d, 64)));
-        if ((threadIdx.x & 63u) == 0u) wmax[threadIdx.x >> 6] = rb;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t m = 0u;
-            for (uint32_t w = 0; w < kBlockThreads / 64; ++w) m = max(m, wmax[w]);
-            rr_max[blockIdx.x] = m;
-        }
+    // the largest rr' (non-negative floats order as their bits; a NaN
+    // radius, the test-only pad fill, orders above every number): the
+    // block's maximum into rr_max[blockIdx.x], reduced by max_bits_kernel
+    // (atomics on one word serialise across the XCDs: one per record, or one
+    // per wave, took C5d's 4.9 M records 0.87 ms)
+    __shared__ uint32_t wmax[kBlockThreads / 64];
+    for (int d = 32; d > 0; d >>= 1) rb = max(rb, static_cast<uint32_t>(__shfl_xor(static_cast<int>(rb), d, 64)));
+    if ((threadIdx.x & 63u) == 0u) wmax[threadIdx.x >> 6] = rb;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t m = 0u;
+        for (uint32_t w = 0; w < kBlockThreads / 64; ++w) m = max(m, wmax[w]);
+        rr_max[blockIdx.x] = m;
     }
 }
 
@@ -1061,14 +1037,13 @@ __global__ void __launch_bounds__(kBlockThreads)
 }
 
 hipError_t launch_shd_screen(const float4* prim_sp, uint32_t n, const float e[6], double delta,
-                             float4* out, float2* out8, uint32_t* rr_max, hipStream_t st) {
+                             float2* out8, uint32_t* rr_max, hipStream_t st) {
     // rr_max: (blocks + 1) words, the scene's largest rr' bits in the last
     if (n) {
         const uint32_t nb = (n + kBlockThreads - 1) / kBlockThreads;
         hipLaunchKernelGGL(shd_screen_kernel, dim3(nb), dim3(kBlockThreads), 0, st, prim_sp, n, e[0],
-                           e[1], e[2], e[3], e[4], e[5], delta, out, out8, rr_max);
-        if (out8)
-            hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(kBlockThreads), 0, st, rr_max, nb, rr_max + nb);
+                           e[1], e[2], e[3], e[4], e[5], delta, out8, rr_max);
+        hipLaunchKernelGGL(max_bits_kernel, dim3(1), dim3(kBlockThreads), 0, st, rr_max, nb, rr_max + nb);
     }
     return hipGetLastError();
 }
@@ -1325,17 +1300,12 @@ static void launch_waveq(K kernel, const FrameArgs& a, size_t lds, hipStream_t s
 
 // Sorted rounds (above): a wave-queue frame of one pixel per wave and 2..4
 // rounds, wherever the per-wave LDS still lets 8 workgroups share a CU.
-// RT_SORT=0 turns it off (A/B; images and counters are the same).
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-    const char* e = getenv(name);
-    return e && *e ? static_cast<uint32_t>(strtoul(e, nullptr, 10)) : dflt;
-}
+// `on`: false under the test hook RT_SORT=0 (images and counters are the same).
 size_t sort_lds_bytes(const FrameArgs& a) {
     return static_cast<size_t>(stack_levels(a.sc, true)) * kBlockThreads * sizeof(uint2) +
            (kBlockThreads / 64) * kSortWaveBytes + kLeafBufBytes;
 }
-static bool sorted_rounds(const FrameArgs& a) {
-    static const uint32_t on = env_u32("RT_SORT", 1u);
+static bool sorted_rounds(const FrameArgs& a, bool on) {
     return on && a.spp >= 8u && a.spw == 64u && a.rounds >= 2u && a.rounds <= kSortMaxRounds &&
            sort_lds_bytes(a) * 8u <= 160u * 1024u &&
            (a.accum != nullptr || a.variant == kVariantWaveQ);
@@ -1344,8 +1314,8 @@ static bool sorted_rounds(const FrameArgs& a) {
 // kOcc: the plain (counter-free) instances answer shadow rays from the
 // scene's occluder lists; stats frames walk either way
 template <bool kTiles, bool kOcc>
-static void launch_scene_o(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStream_t st) {
-    if (sorted_rounds(a)) {
+static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t lds, hipStream_t st) {
+    if (sorted_rounds(a, sort)) {
         const size_t sl = sort_lds_bytes(a);
         if (a.accum) {
             if (a.count_work)
@@ -1414,11 +1384,11 @@ static void launch_scene_o(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStr
 // one-lane uniform leaves, bundle prefilter, 6- and 8-wave builds) were
 // removed in round 3; their A/B logs stay under profiles/.
 template <bool kTiles>
-static void launch_scene_t(const FrameArgs& a, uint32_t n_bt, size_t lds, hipStream_t st) {
+static void launch_scene_t(const FrameArgs& a, bool sort, uint32_t n_bt, size_t lds, hipStream_t st) {
     if (a.sc.prim_occ && a.sc.occ_sp && a.shadows && !a.count_work)
-        launch_scene_o<kTiles, true>(a, n_bt, lds, st);
+        launch_scene_o<kTiles, true>(a, sort, n_bt, lds, st);
     else
-        launch_scene_o<kTiles, false>(a, n_bt, lds, st);
+        launch_scene_o<kTiles, false>(a, sort, n_bt, lds, st);
 }
 
 bool variant_available(uint32_t v) {
@@ -1426,7 +1396,8 @@ bool variant_available(uint32_t v) {
            v == kVariantWaveQ || v == kVariantWaveQLow;
 }
 
-hipError_t launch_scene(const FrameArgs& a_in, hipStream_t st) {
+// sort: sorted rounds where they apply (the renderer's; off only under a test hook)
+hipError_t launch_scene(const FrameArgs& a_in, bool sort, hipStream_t st) {
     FrameArgs a = a_in;
     if (a.accum) a.variant = kVariantLaneUnified;  // what launch_scene_t runs (LDS sizing)
     // wave mapping: spw samples x ppw pixels per wave (see scene_kernel)
@@ -1440,9 +1411,9 @@ hipError_t launch_scene(const FrameArgs& a_in, hipStream_t st) {
     a.wq_chunk = ck ? 1u << (ck - 1u) : std::max(1u, 4u / std::max(1u, std::min(a.rounds, 4u)));
     const size_t lds = scene_lds_bytes(a);
     if (a.tiles)
-        launch_scene_t<true>(a, 0, lds, st);
+        launch_scene_t<true>(a, sort, 0, lds, st);
     else
-        launch_scene_t<false>(a, 0, lds, st);
+        launch_scene_t<false>(a, sort, 0, lds, st);
     return hipGetLastError();
 }
 

@@ -96,11 +96,11 @@ enum BlockStat : uint32_t {
     kBsExactLoad,     // chunks whose camera-relative screen passed: 2 sphere loads for the exact tests
     kBsPastEnd,       // chunks whose slot 1 lies past the leaf's end (lanes: how many)
     kBsTieLoad,       // exact-t ties: 2 prim_idx loads
-    kBsHitIdx,        // nearest walks ending on a hit: 1 prim_idx load
+    kBsHitIdx,        // (unused since shading by leaf reference; kept: tools index this enum)
     kBsShadeLoad,     // shading reads of a hit's sphere record / albedo (1 load each)
     kBsChunkShadow,   // leaf chunk trips of shadow (any-hit) walks
     kBsJumpDescendShadow,  // jump mid-plane steps of shadow walks
-    kBsLdsLeaf,       // leaf visits staged through the wave's LDS buffer (RT_LDS_LEAF)
+    kBsLdsLeaf,       // leaf visits staged through the wave's LDS buffer
     kBlockStats
 };
 
@@ -193,15 +193,13 @@ struct SceneArgs {
     const float4* prim_cam;
     // Light-plane screen records (DESIGN.md 5.1 "Light-plane screen"): per leaf
     // reference {u, v} = the centre's coordinates in the plane perpendicular
-    // to the light direction L (basis FrameArgs::shd_e) and rr' >= (r + slack)^2,
-    // made once per scene and light (shd_screen_kernel).  Shadow rays (any-hit,
-    // direction L) screen a sphere by (u_p - u)^2 + (v_p - v)^2 <= rr'.
-    const float4* prim_shd;
-    // The same records in 8 bytes, {u, v} per reference (RT_SHD8): one
-    // dwordx4 carries a chunk's two; the radius term is the scene's largest
-    // rr' (FrameArgs::shd_rr), so the screen passes a superset still
+    // to the light direction L (basis FrameArgs::shd_e), 8 bytes, made once
+    // per scene and light (shd_screen_kernel): one dwordx4 carries a chunk's
+    // two.  Shadow rays (any-hit, direction L) screen a sphere by
+    // (u_p - u)^2 + (v_p - v)^2 <= rr', rr' >= (r + slack)^2 the scene's
+    // largest (FrameArgs::shd_rr), so every sphere's own bound passes too
     const float2* prim_shd8;
-    // Image-plane screen records of primary rays in 8 bytes (RT_CAM8): per
+    // Image-plane screen records of primary rays in 8 bytes: per
     // reference {qx, qy}, the sphere centre's gnomonic projection in the
     // basis FrameArgs::cam8_B, with a bf16 bound rho^2 on the image-plane
     // distance of every ray the exact test may accept folded into the low
@@ -212,10 +210,10 @@ struct SceneArgs {
     // hit is shaded from prim_sp[ref] and prim_al[ref], lines the walk's own
     // exact test and its neighbours just read, instead of three dependent
     // loads of lines by sphere index (prim_idx, spheres, albedo) that miss the
-    // L2 (RT_REF_SHADE)
+    // L2
     const uint32_t* prim_al;
     // LDS leaf staging: leaves of kLdsLeafMin .. lds_max - 1
-    // spheres are staged; kLeafBuf, or 0 (off) under RT_LDS_STAGE=0 (A/B:
+    // spheres are staged; kLeafBuf, or 0 (off) under the test hook RT_LDS_STAGE=0 (A/B:
     // off at run time loses on every config, C5d included,
     // profiles/r05/stage_switch_ab.log)
     uint32_t lds_max;

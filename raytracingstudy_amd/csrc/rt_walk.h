@@ -79,15 +79,6 @@ __device__ __forceinline__ float isect_h(float o0, float o1, float o2, float d0,
     return isect_h_oc(ocx, ocy, ocz, d0, d1, d2, sp.w);
 }
 
-// Camera-relative records (SceneArgs::prim_cam): 0 off; 1 =
-// {o - c, C'} with the slack screen fma(b, b, -C') >= 0 and the exact tests
-// reloading the chunk's spheres; 2 = {o - c, r}, the exact discriminant from
-// the stored o - c (isect's own operations, 10 VALU: no slack, no reload)
-#ifndef RT_CAM_MODE
-#define RT_CAM_MODE 1
-#endif
-constexpr int kCamMode = RT_CAM_MODE;
-
 // The kernel's FrameArgs as memory (the kernarg segment, scalar-cached),
 // behind an opaque pointer: a field read through it is a fresh s_load at that
 // point instead of a value kept live in an SGPR across the walk (the register
@@ -123,85 +114,22 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
 }
 
-// LDS leaf staging (RT_LDS_LEAF): a per-wave buffer of
-// kLeafBuf spheres after the rest of the workgroup's LDS (pixel sums and
-// stacks, or the sorted path's stacks and per-wave regions).
-#ifndef RT_LDS_LEAF
-#define RT_LDS_LEAF 1
-#endif
+// LDS leaf staging: a per-wave buffer of kLeafBuf spheres
+// after the rest of the workgroup's LDS (pixel sums and stacks, or the sorted
+// path's stacks and per-wave regions).  Used by the nearest walks that screen
+// 16-byte camera-relative records: the block-tile queue (variants 7 and 10)
+// and progressive frames below 8 spp.
 // Leaves of fewer spheres read them directly: staging adds an LDS round trip
 // to the first chunk, which a leaf of one or two chunks does not win back.
 // Measured (profiles/r05/ldsmin_ab.log, 3 alternating rounds, against no
 // staging): from 1 / 4 / 6 / 8 spheres C3 +1.0 / -0.7 / -1.7 / +0.2%, C5
 // -6.9 / -7.8 / -7.8 / -5.3%, C5d +4.0 / +2.5 / +2.3 / +2.5%.  Round 6, with
-// shadow walks no longer staging (kLdsShadow), against 6: from 2 / 3 / 4 / 5
-// spheres C3 +0.2 / -0.4 / -0.5 / -1.0%, C5 -0.8 / -1.1 / -1.2 / -1.3%, C5d
-// +1.0 / +0.5 / +0.3 / +0.1%, 8: C3 +3.5%, C5 +4.6%
+// shadow walks no longer staging, against 6: from 2 / 3 / 4 / 5 spheres C3
+// +0.2 / -0.4 / -0.5 / -1.0%, C5 -0.8 / -1.1 / -1.2 / -1.3%, C5d +1.0 / +0.5
+// / +0.3 / +0.1%, 8: C3 +3.5%, C5 +4.6%
 // (profiles/r06/ab_r6_lmin2_lmin3_lmin4_lmin5.log, ab_r6_lmin4_lmin8.log).
-#ifndef RT_LDS_MIN
-#define RT_LDS_MIN 5
-#endif
-constexpr uint32_t kLdsLeafMin = RT_LDS_MIN;
-// Only nearest-hit (primary) walks stage their leaves: a shadow ray may stop
-// at a leaf's first chunk, after a staging load fetched all of the leaf's
-// lines, and its chunked reads stop with it.  Against staging shadow leaves
-// too (RT_LDS_SHADOW=1, A/B): C5d -1.3%, C5 -0.5%, C3 -0.1%
-// (profiles/r06/ab_ctr3_noshst_sbo.log, 3 alternating rounds).
-#ifndef RT_LDS_SHADOW
-#define RT_LDS_SHADOW 0
-#endif
-constexpr bool kLdsShadow = RT_LDS_SHADOW != 0;
-// Shading by leaf reference (SceneArgs::prim_al): a nearest walk's `iout` is
-// the hit's reference, and shading reads prim_sp[ref] / prim_al[ref]; 0 keeps
-// the sphere index (prim_idx[ref]) and the by-index spheres / albedo arrays.
-// Measured (profiles/r06/ab_ref_shade.log, 3 alternating rounds): C3 -0.7%,
-// C5 -0.5%, C5d -0.2%, C2 0; L2 misses C3 -7.5%, C5d -11.5% (pmc_l2_*.json)
-#ifndef RT_REF_SHADE
-#define RT_REF_SHADE 1
-#endif
-// Light-plane records in 8 bytes (SceneArgs::prim_shd8): a shadow chunk's two
-// spheres in ONE dwordx4 (the texture path charges a load by instruction,
-// not by bytes: 16 cycles for a dwordx2 or a dwordx4), screened against the
-// scene's largest radius term.  C3 -2.0%, C5 -2.4%, C2 -2.8%, C5d -0.1%; the
-// looser radius sends 2% (C3, C5) to 6% (C5d) more shadow chunks down the
-// exact path (profiles/r06/ab_shd8.log, bstats_shd8.log).  0: 16-byte records
-#ifndef RT_SHD8
-#define RT_SHD8 1
-#endif
-// Image-plane screen for primary rays in 8 bytes (SceneArgs::prim_cam8,
-// DESIGN.md 5.1 round 6): the primary walks screen a chunk's two spheres
-// from ONE dwordx4 instead of two 16-byte camera-relative records, and stage
-// no leaves in LDS.  C3 -2.9%, C5 -2.4%, C5d -2.1%, C2 -1.9% (unsorted and
-// sorted walks, profiles/r06/ab_cam8_sorted.log); RT_CAM8=0: the 16-byte
-// camera-relative screen and its LDS staging
-#ifndef RT_CAM8
-#define RT_CAM8 1
-#endif
-// ... LDS staging of the 8-byte records, pairs per float4, from
-// kLdsLeafMin8 spheres: C3 +1.2 / +1.3 / +3.4% from 8 / 5 / 3 against none
-// (ab_cam8_staging.log), so off
-#ifndef RT_CAM8_LDS
-#define RT_CAM8_LDS 0
-#endif
-// ... for the sorted walks (C5, C5d) too
-#ifndef RT_CAM8_SORTED
-#define RT_CAM8_SORTED 1
-#endif
-#ifndef RT_CAM8_LDS_MIN
-#define RT_CAM8_LDS_MIN 5
-#endif
-constexpr uint32_t kLdsLeafMin8 = RT_CAM8_LDS_MIN;
-// ... each sphere's own rr' as bf16 in the records' low bytes (RT_SHD8_PER)
-// instead of the scene's largest
-#ifndef RT_SHD8_PER
-#define RT_SHD8_PER 0
-#endif
-// spheres per chunk of the shadow walks (with 8-byte records: two per dwordx4);
-// 4 spills 48-100 B and runs C3 +6%, C5 +8%, C5d +5% (profiles/r06/ab_shd_chunk4.log)
-#ifndef RT_SHD_CHUNK
-#define RT_SHD_CHUNK 2
-#endif
-constexpr size_t kLeafBufBytes = RT_LDS_LEAF ? (kBlockThreads / 64u) * kLeafBuf * sizeof(float4) : 0u;
+constexpr uint32_t kLdsLeafMin = 5;
+constexpr size_t kLeafBufBytes = (kBlockThreads / 64u) * kLeafBuf * sizeof(float4);
 
 // Ancestor-stack levels per thread: depths 1..D-1, or K..D-1 with a cell table
 // (a pop above depth K jumps through the table instead).
@@ -227,37 +155,6 @@ __device__ __forceinline__ uint32_t leaf_buf_base(const SceneArgs& S, bool sorte
     return head + wave * kLeafBuf;
 }
 
-#ifndef RT_CAP_VALU
-#define RT_CAP_VALU 0
-#endif
-
-// LDS leaf staging by gfx950's direct global -> LDS load (RT_GLDS, VERDICT r05
-// item 5): ONE global_load_lds_dwordx4 writes spheres 0 .. cnt - 1 of the leaf
-// at src into dst[0 .. cnt - 1] without a VGPR round trip or a ds_write.  Its
-// LDS destination is M0 + 16 x lane id, so it needs cnt consecutive active
-// lanes: from the wave's first active lane l0, lane l0 + k fetches sphere k
-// into (dst - l0)[l0 + k].  Returns false (the caller stages through
-// registers) when lanes l0 .. l0 + cnt - 1 are not all active.  (Widening
-// exec to lanes 0 .. cnt - 1 inside an asm statement instead, the first
-// build, was wrong: the address temporary's VGPR then changes in lanes the
-// compiler keeps other lanes' loop-exit values in; plain frames differed.)
-// The explicit vmcnt(0) retires the DMA before the chunks' ds_reads (the
-// issuing wave is the reader: no barrier, MI355X_MICROARCH.md item 7).
-#ifndef RT_GLDS
-#define RT_GLDS 0
-#endif
-__device__ __forceinline__ bool glds_leaf(const float4* src, float4* dst, uint32_t cnt) {
-    typedef __attribute__((address_space(3))) void LdsV;
-    const uint64_t act = __ballot(1);
-    const uint32_t l0 = static_cast<uint32_t>(__builtin_ctzll(act));
-    const uint64_t run = ((1ull << cnt) - 1ull) << l0;  // cnt < kLeafBuf = 32
-    if (l0 + cnt > 64u || (act & run) != run) return false;
-    const uint32_t k = __lane_id() - l0;
-    if (k < cnt) __builtin_amdgcn_global_load_lds(src + k, (LdsV*)(dst - l0), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return true;
-}
-
 // Grid-space octree walk (DESIGN.md "Octree walk"): mirrored origin so every
 // direction component is >= 0 (the Revelles entry step of hit_sphere,
 // src/renderer.cu:23-43), cell planes at integer grid coordinates, descend by
@@ -277,7 +174,13 @@ __device__ __forceinline__ bool glds_leaf(const float4* src, float4* dst, uint32
 // (the lanes are incoherent), and NO read through kernargs(): every such read
 // below sits behind a condition that is false at compile time in this mode.
 // Both kinds return the hit's leaf REFERENCE in `iout` (an any-hit walk of a
-// frame sets `tout` only); the caller maps it through prim_idx.
+// frame sets `tout` only); the caller maps it through prim_idx, or shades by
+// reference (prim_sp[ref], SceneArgs::prim_al[ref]: against the sphere index
+// and the by-index arrays C3 -0.7%, C5 -0.5%, L2 misses C3 -7.5%, C5d -11.5%,
+// profiles/r06/ab_ref_shade.log).
+// lb_u: the wave's LDS leaf buffer (scene_body's leaf_buf_base), read only by
+// a walk that stages leaves: a frame's nearest walk without kCam8.  The other
+// walks pass none.
 template <bool kAnyHitT, int kChunk = 2, bool kDynAny = false, bool kStats = true,
           bool kNoStack = false, bool kShadowL = false, bool kCam8 = false, bool kGeneric = false>
 __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, float o2, float d0,
@@ -297,11 +200,17 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
     // chunk that passes load the chunk's own sphere records (through a fresh
     // kernel-argument read: no second array pointer lives in the walk).
     // Shadow (any-hit) walks start at hit points and keep the full screen.
-    const bool cam = !kGeneric && kCamMode != 0 && !kAnyHit;
-    const bool cam_exact = cam && kCamMode == 2;  // records {o - c, r}: the tests use them as they are
-    // 8-byte image-plane records (RT_CAM8, unsorted nearest walks): the
-    // lane's point s = (Bd).xy / (Bd).z, once per walk
-    const bool cam8 = kCam8 && cam && !cam_exact && kChunk % 2 == 0;
+    // (Exact records {o - c, r} instead, the discriminant from the stored
+    // o - c with no slack and no reload, gained less: C3 -1.7% against -2.9%,
+    // profiles/r05/screen_ab.log.)
+    const bool cam = !kGeneric && !kAnyHit;
+    // Image-plane screen in 8 bytes (kCam8; SceneArgs::prim_cam8, DESIGN.md
+    // 5.1 round 6): the wave-queue walks, sorted and not, screen a chunk's two
+    // spheres from ONE dwordx4 instead of two 16-byte camera-relative records
+    // and stage no leaves in LDS: C3 -2.9%, C5 -2.4%, C5d -2.1%, C2 -1.9%
+    // (profiles/r06/ab_cam8_sorted.log).  The lane's point s = (Bd).xy /
+    // (Bd).z, once per walk
+    const bool cam8 = kCam8 && cam;
     float s8x = 0.0f, s8y = 0.0f;
     if (cam8) {
         KernArgs* kb = kernargs();
@@ -317,23 +226,24 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
     // near the ray's origin in the plane perpendicular to L.  The records
     // hold each centre's {u, v} there and a radius grown by the rounding
     // bound, the lane its origin's {up, vp}: 5 VALU a sphere instead of 13.
-#ifdef RT_NO_SHADOW_SCREEN
-    constexpr bool kShdOk = false;
-#else
-    constexpr bool kShdOk = true;
-#endif
-    const bool shd = kShdOk && kShadowL && kAnyHit;  // a shadow ray along L (the caller says so)
+    // The records are 8 bytes (SceneArgs::prim_shd8), a chunk's two spheres
+    // in ONE dwordx4 (the texture path charges a load by instruction, not by
+    // bytes), screened against the scene's largest radius term shd_rr: C3
+    // -2.0%, C5 -2.4%, C2 -2.8%, C5d -0.1% against 16-byte records with each
+    // sphere's own (profiles/r06/ab_shd8.log).  Each sphere's own as bf16 in
+    // the records' low bytes: C3 +0.5%, C5 +0.3%, C5d +0.1%
+    // (profiles/r06/ab_shd8_per_sphere.log).
+    const bool shd = kShadowL && kAnyHit;  // a shadow ray along L (the caller says so)
     float up = 0.0f, vp = 0.0f;
-    const bool shd8 = RT_SHD8 && kChunk % 2 == 0 && shd;
-    const float2* __restrict__ shd8_base = shd8 ? S.prim_shd8 : nullptr;
+    const float2* __restrict__ shd8_base = shd ? S.prim_shd8 : nullptr;
     const float2* __restrict__ cam8_base = cam8 ? kernargs()->sc.prim_cam8 : nullptr;
-    const float shd_rr = shd8 ? kernargs()->shd_rr : 0.0f;
+    const float shd_rr = shd ? kernargs()->shd_rr : 0.0f;
     if (shd) {
         KernArgs* ke = kernargs();
         up = fmaf(o2, ke->shd_e[2], fmaf(o1, ke->shd_e[1], o0 * ke->shd_e[0]));
         vp = fmaf(o2, ke->shd_e[5], fmaf(o1, ke->shd_e[4], o0 * ke->shd_e[3]));
     }
-    const float4* __restrict__ prim_sp = cam ? S.prim_cam : shd ? S.prim_shd : S.prim_sp;
+    const float4* __restrict__ prim_sp = cam ? S.prim_cam : S.prim_sp;
     const uint2* __restrict__ nodes = S.nodes;
     const float o[3] = {o0, o1, o2};
     const float d[3] = {d0, d1, d2};
@@ -387,8 +297,7 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
         RT_BS(kBsTest);
         if (kAnyHit) RT_BS(kBsTestShadow);
         float th;
-        if (cam_exact ? isect_oc(sp.x, sp.y, sp.z, d0, d1, d2, sp.w, tmin, tmax, th, bs)
-                      : isect(o0, o1, o2, d0, d1, d2, sp, tmin, tmax, th, bs)) {
+        if (isect(o0, o1, o2, d0, d1, d2, sp, tmin, tmax, th, bs)) {
             RT_BS(kBsAccept);
             if (kAnyHit) {
                 tout = th;
@@ -409,9 +318,7 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
     // oracle): each lane loads its own, kChunk loads in flight.
     // The chunk loop over one leaf's spheres (offset off, count cnt), each
     // read as load(k), k counted from the leaf's first reference.
-    // plb: with 8-byte image-plane records staged in LDS (RT_CAM8_LDS), the
-    // wave's buffer, pairs of records per float4; ~0u: records from global
-    auto chunks = [&](auto&& load, uint32_t off, uint32_t cnt, uint32_t plb = ~0u) -> bool {
+    auto chunks = [&](auto&& load, uint32_t off, uint32_t cnt) -> bool {
         // cnt >= 1 (a leaf is a non-empty cell; the root leaf is guarded by
         // its caller): a do-while skips the loop-entry test and its branch
         uint32_t j = 0;
@@ -428,37 +335,27 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
             // kChunk unconditional dwordx4 loads in flight at fixed offsets; a
             // slot past the leaf's end reads the next leaf or the array's
             // kPrimPad tail (in bounds) and is never tested
+            // (fetching slot q >= 1 only when some lane's leaf still holds
+            // it, a wave-uniform branch: C3 +8.0%, C5 +7.3%, C5d +7.5%,
+            // profiles/r05/lds_pastend_ab.log)
             float4 sv[kChunk];
-            // slot q >= 1 is fetched only when some lane's leaf still holds
-            // it (RT_SKIP_PAST_END, a wave-uniform branch): a wave-wide load
-            // costs the texture path as much for one lane as for 64, and at
-            // a leaf's odd end the whole wave usually has no slot 1
-            bool fetched[kChunk];
-            if (shd8 || cam8) {
+            if (shd || cam8) {
                 // two slots' 8-byte records per dwordx4 (8-byte aligned:
-                // global loads need dword alignment only; an even kChunk)
+                // global loads need dword alignment only).  Staged in LDS
+                // instead, pairs per float4, from 8 / 5 / 3 spheres: C3 +1.2 /
+                // +1.3 / +3.4% (profiles/r06/ab_cam8_staging.log)
+                static_assert(!(kCam8 || kShadowL) || kChunk % 2 == 0, "two 8-byte records per load");
 #pragma unroll
                 for (int h = 0; h < kChunk / 2; ++h) {
-                    extern __shared__ __attribute__((aligned(16))) float4 lds_pairs[];
-                    const float4 pr = cam8 && plb != ~0u
-                                          ? lds_pairs[plb + (j >> 1) + h]
-                                          : *reinterpret_cast<const float4*>((cam8 ? cam8_base : shd8_base) +
-                                                                             (off + j + 2u * h));
+                    const float4 pr = *reinterpret_cast<const float4*>((cam8 ? cam8_base : shd8_base) +
+                                                                       (off + j + 2u * h));
                     sv[2 * h] = make_float4(pr.x, pr.y, 0.0f, 0.0f);
                     sv[2 * h + 1] = make_float4(pr.z, pr.w, 0.0f, 0.0f);
-                    fetched[2 * h] = fetched[2 * h + 1] = true;
                 }
             } else
 #pragma unroll
             for (int q = 0; q < kChunk; ++q) {
-#ifdef RT_SKIP_PAST_END
-                fetched[q] = q == 0 || __any(in_leaf(q));
-                if (fetched[q]) sv[q] = load(j + q);
-                else sv[q] = sv[0];
-#else
-                fetched[q] = true;
                 sv[q] = load(j + q);
-#endif
                 // issue in list order, so the first test waits for its own
                 // sphere only (vmcnt(kChunk-1)), not for the whole chunk
                 __builtin_amdgcn_sched_barrier(0);
@@ -476,9 +373,7 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
                 // exact tests below still skip it (in_leaf), so it can only
                 // send the chunk down the exact path for nothing
                 bool pos;
-                if (cam_exact) {
-                    pos = !(isect_h_oc(sv[q].x, sv[q].y, sv[q].z, d0, d1, d2, sv[q].w) < 0.0f);
-                } else if (cam8) {
+                if (cam8) {
                     // the lane's image-plane distance from the centre's
                     // projection against rho^2 (bf16 in the records' low bytes)
                     const float rho2 = __uint_as_float(__builtin_amdgcn_perm(
@@ -495,15 +390,11 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
                     // the centre's light-plane distance from the origin; rr'
                     // covers the rounding, so every sphere isect accepts passes
                     const float du = up - sv[q].x, dv = vp - sv[q].y;
-                    const float rr8 = RT_SHD8_PER ? __uint_as_float(__builtin_amdgcn_perm(
-                                                         __float_as_uint(sv[q].x), __float_as_uint(sv[q].y),
-                                                         0x04000C0Cu))
-                                                   : shd_rr;
-                    pos = !(fmaf(dv, dv, du * du) > (shd8 ? rr8 : sv[q].z));
+                    pos = !(fmaf(dv, dv, du * du) > shd_rr);
                 } else {
                     pos = !(isect_h(o0, o1, o2, d0, d1, d2, sv[q]) < 0.0f);
                 }
-                maybe |= fetched[q] && pos;
+                maybe |= pos;
             }
             // marked unlikely (it is: most chunks pass no lane): the exact
             // tests are laid out off the fall-through path (C3 -0.6%, C5
@@ -512,7 +403,7 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
             if (j + 1u >= cnt) RT_BS(kBsPastEnd);
 #endif
             if (__builtin_expect(__any(maybe), 0)) {
-                if ((cam && !cam_exact) || shd) {  // the exact tests need the spheres themselves (cam8 too)
+                if (cam || shd) {  // the exact tests need the spheres themselves (cam8 too)
                     RT_BS(kBsExactLoad);
                     const float4* __restrict__ ex = kernargs()->sc.prim_sp + off;
 #pragma unroll
@@ -531,7 +422,6 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
     auto leaf = [&](uint32_t off, uint32_t cnt) -> bool {
         static_assert(kChunk <= kPrimPad + 1, "leaf loads may run kChunk-1 spheres past a leaf");
         RT_BS(kBsLeaf);
-#if RT_LDS_LEAF
         // A leaf the whole wave is at (the common case: one pixel's samples
         // walk together): its spheres cross the texture path ONCE, each
         // active lane fetching one into the wave's LDS leaf buffer, and the
@@ -541,39 +431,36 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
         // is a typed LDS array, never a generic pointer (round 3's flat
         // loads).  A slot past the leaf's end holds a stale sphere, which
         // the exact tests skip as before.
+        // Only nearest-hit walks stage: a shadow ray may stop at a leaf's
+        // first chunk, after a staging load fetched all of the leaf's lines.
+        // Against staging shadow leaves too: C5d -1.3%, C5 -0.5%, C3 -0.1%
+        // (profiles/r06/ab_ctr3_noshst_sbo.log).
+        // The fill goes through registers (a ds_write per record).  gfx950's
+        // direct global -> LDS load instead, one global_load_lds_dwordx4 for a
+        // run of active lanes: C3 +0.9%, C5 +1.3%, C5d +0.1%
+        // (profiles/r06/ab_ctr2_glds_pack.log); its first build faulted a GPU
+        // (a sign-extended address half, pack_ab_glds_fault.log).
         const uint32_t off_u = __builtin_amdgcn_readfirstlane(off);
         const uint32_t cnt_u = __builtin_amdgcn_readfirstlane(cnt);
-        if (!kGeneric && (kLdsShadow || !kAnyHit) && !cam8 && cnt_u >= kLdsLeafMin && cnt_u < kernargs()->sc.lds_max &&
+        if (!kGeneric && !kAnyHit && !cam8 && cnt_u >= kLdsLeafMin && cnt_u < kernargs()->sc.lds_max &&
             __all(off == off_u)) {
             RT_BS(kBsLdsLeaf);
             extern __shared__ __attribute__((aligned(16))) float4 lds_leaf[];
-            // (lb_u: the caller's wave-uniform copy, an SGPR; else from threadIdx)
+            // lb_u is scene_body's wave-uniform copy (an SGPR) in every frame
+            // kernel, so the test below never fails.  It stays because the
+            // block-tile-queue kernels are scheduled around it: with lb_u used
+            // as it is, variant 10 runs C3 +0.7 / +1.3% and variant 7 +1.2 /
+            // -0.1% (profiles/r08/ab_block_tile_queue_split.log), and this
+            // way their machine code is the one measured so far
             const uint32_t lb = lb_u != ~0u ? lb_u : leaf_buf_base(S, kNoStack);
             const float4* __restrict__ pu = prim_sp + off_u;
-            if (!RT_GLDS || !glds_leaf(pu, lds_leaf + lb, cnt_u)) {
-                const uint64_t act = __ballot(1);
-                const uint32_t na = static_cast<uint32_t>(__popcll(act));
-                for (uint32_t k = lane_rank(act); k < cnt_u; k += na) lds_leaf[lb + k] = pu[k];
-            }
+            const uint64_t act = __ballot(1);
+            const uint32_t na = static_cast<uint32_t>(__popcll(act));
+            for (uint32_t k = lane_rank(act); k < cnt_u; k += na) lds_leaf[lb + k] = pu[k];
             // (a wave's LDS operations complete in order: the reads below see
             // the writes, and the compiler keeps them in order: same array)
             return chunks([&](uint32_t k) { return lds_leaf[lb + k]; }, off_u, cnt_u);
         }
-        // the same for 8-byte image-plane records: pairs of records, one
-        // float4 per active lane, the chunks reading a pair per ds_read_b128
-        if (RT_CAM8_LDS && cam8 && cnt_u >= kLdsLeafMin8 && cnt_u < 2u * kernargs()->sc.lds_max &&
-            __all(off == off_u)) {
-            RT_BS(kBsLdsLeaf);
-            extern __shared__ __attribute__((aligned(16))) float4 lds_leaf[];
-            const uint32_t lb = lb_u != ~0u ? lb_u : leaf_buf_base(S, kNoStack);
-            const float4* __restrict__ pu = reinterpret_cast<const float4*>(cam8_base + off_u);
-            const uint32_t np = (cnt_u + 1u) >> 1;  // pairs (an odd leaf's last pair reads one past it)
-            const uint64_t act = __ballot(1);
-            const uint32_t na = static_cast<uint32_t>(__popcll(act));
-            for (uint32_t k = lane_rank(act); k < np; k += na) lds_leaf[lb + k] = pu[k];
-            return chunks([&](uint32_t k) { return lds_leaf[lb + k]; }, off_u, cnt_u, lb);
-        }
-#endif
         const float4* __restrict__ ps = prim_sp + off;
         return chunks([&](uint32_t k) { return ps[k]; }, off, cnt);
     };
@@ -603,17 +490,11 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
         // root-left conditions are OR-ed into one flag, so the wave's exec
         // bookkeeping is one loop-exit mask update per trip (the scalar pipe is
         // this kernel's busiest unit, profiles/r02/pmc_sq_screen.json).
+        // (The trip counter as a lane value, so that the cap test is a VALU
+        // compare: SALU -4.0% as predicted, time C3 -0.6 / 0.0%, C5d +0.7%:
+        // the scalar pipe does not bind.  profiles/r06/capv_ab.log)
         bool any_hit = false;
-#if RT_CAP_VALU
-        // the trip counter as a lane value (an opaque v_mov): the cap test is
-        // one VALU compare feeding the exit mask, not SALU add / compare /
-        // select on the scalar pipe (A/B)
-        uint32_t it;
-        asm volatile("v_mov_b32 %0, 0" : "=v"(it));
-        for (const uint32_t cap = 8u * G + 64u;; ++it) {
-#else
         for (uint32_t it = 0, cap = 8u * G + 64u;; ++it) {
-#endif
             RT_BS(kBsIter);
             if (kAnyHit) RT_BS(kBsIterShadow);
             uint2 rec = make_uint2(0u, 0u);
@@ -755,9 +636,8 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
         if (any_hit) return true;
     }
     if (!kAnyHit && best_ref != kNoHit) {
-        if (!RT_REF_SHADE) RT_BS(kBsHitIdx);
         tout = best_t;
-        iout = RT_REF_SHADE || kGeneric ? best_ref : S.prim_idx[best_ref];
+        iout = best_ref;
         return true;
     }
     return false;
@@ -768,13 +648,12 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
 // kernel's 64-VGPR budget and the kernel inherits its count (5 waves per SIMD).
 template <bool kNoStack>
 __device__ __forceinline__ bool shadow_walk_fallback(const SceneArgs& S, float o0, float o1, float o2,
-                                                  uint2* __restrict__ stk, uint32_t lb_u) {
+                                                  uint2* __restrict__ stk) {
     KernArgs* kl = kernargs();
     float ts;
     uint32_t is, nn = 0, np = 0;
-    return walk<true, RT_SHD_CHUNK, false, false, kNoStack, true>(
-        S, o0, o1, o2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, ts, is, nn, np, stk, true,
-        nullptr, lb_u);
+    return walk<true, 2, false, false, kNoStack, true>(
+        S, o0, o1, o2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, ts, is, nn, np, stk, true);
 }
 
 // A frame's shadow ray from a hit on the sphere of leaf reference `ref`,
@@ -785,8 +664,7 @@ __device__ __forceinline__ bool shadow_walk_fallback(const SceneArgs& S, float o
 // loaded by the caller; lanes whose header says "walk" walk the octree.
 template <bool kNoStack>
 __device__ __forceinline__ bool shadow_occluded(const SceneArgs& S, uint2 hdr, bool active, float o0,
-                                                float o1, float o2, uint2* __restrict__ stk,
-                                                uint32_t lb_u) {
+                                                float o1, float o2, uint2* __restrict__ stk) {
     KernArgs* kl = kernargs();
     const float l0 = kl->L[0], l1 = kl->L[1], l2 = kl->L[2];
     const bool walks = active && hdr.y == kOccWalk;
@@ -799,7 +677,7 @@ __device__ __forceinline__ bool shadow_occluded(const SceneArgs& S, uint2 hdr, b
         occ = isect(o0, o1, o2, l0, l1, l2, sp, 0.0f, INFINITY, th);
     }
     if (__any(walks)) {
-        if (walks) occ = shadow_walk_fallback<kNoStack>(S, o0, o1, o2, stk, lb_u);
+        if (walks) occ = shadow_walk_fallback<kNoStack>(S, o0, o1, o2, stk);
     }
     return occ;
 }

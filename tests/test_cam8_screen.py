@@ -1,7 +1,7 @@
 """The 8-byte image-plane screen of primary rays is sound (CPU; DESIGN.md 5.1
 round 6 "An 8-byte image-plane screen for primary rays").
 
-With RT_CAM8 a primary ray's chunk runs the exact ray-sphere tests only when
+With this screen a primary ray's chunk runs the exact ray-sphere tests only when
 the lane's image-plane point s = (Bd).xy / (Bd).z lies within rho of the
 sphere centre's projection q, both in the frame's basis B (rt_capi.cpp
 cam8_basis), rho^2 stored as bf16 in the low bytes of the 8-byte record

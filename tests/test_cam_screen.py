@@ -201,8 +201,10 @@ def test_shadow_screen_annulus():
 @pytest.mark.parametrize("ld", LIGHTS)
 def test_packed_shadow_screen_never_rejects_an_accepted_sphere(spheres, ld):
     """The same with each sphere's own rr' packed as bf16 into the low bytes of
-    its 8-byte {u, v} record (RT_SHD8_PER, oracle.c orc_shd8_screen_check):
-    no miss at the product's radius, some with it shrunk by 1%."""
+    its 8-byte {u, v} record (oracle.c orc_shd8_screen_check; the kernels'
+    arm of it, RT_SHD8_PER, measured slower and was removed in round 8, the
+    model stays as the record of its soundness): no miss at that radius, some
+    with it shrunk by 1%."""
     L = _kernel_light(ld)
     big_m = _bound(spheres)
     rng = np.random.default_rng(13)

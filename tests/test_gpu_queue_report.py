@@ -127,6 +127,29 @@ def test_test_hooks_need_the_flag(gpu, monkeypatch, capfd):
     assert "RT_TEST_FAULT=queue:0 ignored" in err
 
 
+@pytest.mark.gpu
+def test_ab_switches_need_the_flag(gpu, oracle, monkeypatch, capfd):
+    """The A/B switches RT_SORT, RT_LDS_STAGE, RT_LEAF_PACK and RT_SB_ORDER are
+    test hooks too: without RT_FLAG_TEST_HOOKS a product renderer names each
+    set one on stderr as ignored and renders the oracle's image (64x48 at 128
+    spp: two sorted rounds)."""
+    switches = {"RT_SORT": "0", "RT_LDS_STAGE": "0", "RT_LEAF_PACK": "1", "RT_SB_ORDER": "1"}
+    for name, value in switches.items():
+        monkeypatch.setenv(name, value)
+    monkeypatch.setattr(_lib, "test_flags", _lib.RT_FLAG_TEST_POISON)
+    w, h, spp, n = 64, 48, 128, 2000
+    sp, al = rt.generate_spheres(n, rt.SEED)
+    with _renderer(w, h, spp, n) as r:
+        r.render()
+        img = r.readback()
+        _, K = r.camera()
+    ref8, _, _ = oracle.Scene(sp, al).render(w, h, scene_pose(), K, spp=spp)
+    assert np.array_equal(img, ref8)
+    err = capfd.readouterr().err
+    for name, value in switches.items():
+        assert f"{name}={value} ignored" in err
+
+
 _NEGCTL_SCRIPT = r"""
 import json, sys
 import numpy as np

@@ -120,23 +120,25 @@ def test_wave_queue_claims_in_slot_order(gpu, oracle, case, delay, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [(20000, 64, 48, 64, 7), (20000, 128, 96, 2, 12),
-                                  (30000, 40, 30, 256, 12)],
-                         ids=lambda c: "n%d_%dx%d_s%d_d%d" % c)
-def test_lds_staging_on_and_off(gpu, oracle, case, monkeypatch):
+@pytest.mark.parametrize("case,variant", [
+    pytest.param(c, v, id="n%d_%dx%d_s%d_d%d" % c + ("_v%d" % v if v else ""))
+    for v in (0, 7) for c in [(20000, 64, 48, 64, 7), (20000, 128, 96, 2, 12), (30000, 40, 30, 256, 12)]])
+def test_lds_staging_on_and_off(gpu, oracle, case, variant, monkeypatch):
     """LDS leaf staging changes which path reads a leaf's spheres, never what
-    a frame computes: on (the default) and off (RT_LDS_STAGE=0, read when
-    the scene is built), plain and stats frames give the oracle's image and
-    counters.  (Since the 8-byte screens, RT_CAM8, the default build's walks
-    stage no leaves, so here both settings read globally; the staging path
-    is what RT_CAM8=0 builds run, parity-checked when they were the default,
-    profiles/r06/pytest_*.log.)"""
+    a frame computes: on (the default) and off (the test hook RT_LDS_STAGE=0,
+    read at rt_create), plain and stats frames give the oracle's image and
+    counters.  Variant 7 (the block-tile queue) reaches the staging path: its
+    nearest walks screen 16-byte camera-relative records and stage a leaf of
+    5..31 spheres the whole wave is at, which the 64- and 256-spp cases (one
+    pixel's 64 samples on a wave) make common.  Variant 0 (the default, the
+    wave queue) screens 8-byte records and stages nothing, so for it both
+    settings read globally."""
     n, w, h, spp, depth = case
     sp, al = rt.generate_spheres(n, rt.SEED)
     out = {}
     for stage in ("0", "1"):
         monkeypatch.setenv("RT_LDS_STAGE", stage)
-        with rt.KernelRenderer(w, h, mode="scene", spp=spp, radiance=True) as r:
+        with rt.KernelRenderer(w, h, mode="scene", spp=spp, radiance=True, variant=variant) as r:
             r.resize(w, h)
             r.setPosition(rt.camera.scene_pose())
             r.set_scene(sp, al, max_depth=depth)

@@ -30,7 +30,12 @@ def main():
     ap.add_argument("--variants", default="1,2")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--spp", type=int, default=0, help="override spp")
+    ap.add_argument("--test-hooks", action="store_true",
+                    help="RT_FLAG_TEST_HOOKS on every renderer: the library then reads its A/B "
+                         "switches (RT_SORT, RT_LDS_STAGE, RT_LEAF_PACK, RT_SB_ORDER) from the environment")
     args = ap.parse_args()
+    if args.test_hooks:
+        rt._lib.test_flags = rt._lib.RT_FLAG_TEST_HOOKS
     # a variant spec is "V", "V:OPT", "V:OPT:T", "V:OPT:T:CAP" or "V:OPT:T:CAP:OCC"
     # (OPT = rt_config opt bits, A/B toggles; T = cell-table depth: 0 off, 1..7,
     # absent = chosen from the tree; CAP = octree leaf capacity, absent = the
