@@ -510,7 +510,7 @@ void orc_cam_screen_check(const float o[3], const float* dirs, const float* sp, 
 }
 
 /* Test-only: the product's image-plane screen of primary rays (rt_kernels.hip
- * cam8_screen_kernel and walk<>'s cam8 chunk screen; rt_capi.cpp cam8_basis
+ * cam8_screen_kernel and walk<>'s cam8 chunk screen; rt_frame_math.h cam8_basis
  * makes the basis B, rows x, y, z in f32) against the exact discriminant of
  * isect, for m (direction, sphere) pairs from camera origin o.  The record
  * is made as the kernel makes it (f64, rho^2 as bf16 in the low bytes of
@@ -674,8 +674,8 @@ void orc_shd8_screen_check(const float* origins, const float L[3], const float* 
 }
 
 /* Test-only: the product's light-plane shadow screen (rt_kernels.hip walk<>,
- * shd_screen_kernel; rt_capi.cpp do_render makes the basis) against the
- * exact discriminant of isect, for m (origin, sphere) pairs with the
+ * shd_screen_kernel; rt_frame_math.h light_plane_basis makes the basis)
+ * against the exact discriminant of isect, for m (origin, sphere) pairs with the
  * frame's shadow direction L.  The basis {e1, e2} is made from L as the host
  * makes it (f64, rounded to f32); slack_m scales the 2D slack delta =
  * slack_m u (M + 1e-4) and grow (0 or 4) the radius factors of the record.

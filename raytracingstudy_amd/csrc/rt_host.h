@@ -1,0 +1,340 @@
+// rt_host.h — what the host units of the C-ABI share (internal, never
+// installed): the renderer's state, the error and allocation helpers, the
+// stream-ordering helpers, and the functions the units call across.
+//   rt_capi.cpp   handle lifetime, camera, rt_render and the display binding
+//   rt_scene.cpp  scene upload, octree build, exports
+//   rt_frame.cpp  per-frame preparation and launch, tiles, queries, G-buffer
+//   rt_multi.cpp  the multi-device handle and its RCCL loader
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "../../include/rt.h"
+#include "octree_gpu.h"
+#include "rt_params.h"
+#include "scene_build.h"
+
+struct ncclComm;  // <rccl/rccl.h>'s ncclComm_t is a pointer to it; only rt_multi.cpp includes that
+
+namespace rtamd {
+
+// the kernels' launchers (rt_kernels.hip, rt_query.hip, rt_gbuffer.hip)
+hipError_t launch_compat(const FrameArgs& a, hipStream_t st);
+hipError_t launch_scene(const FrameArgs& a, bool sort, hipStream_t st);
+bool variant_available(uint32_t v);
+hipError_t launch_unpack(const uint32_t* packed, const uint32_t* tiles, uint32_t n_tiles,
+                         uint32_t ts, uint32_t tiles_x, uint32_t W, uint32_t H, uint32_t* img,
+                         hipStream_t st);
+hipError_t launch_cam_screen(const float4* prim_sp, uint32_t n, const float o[3], float4* out,
+                             hipStream_t st);
+hipError_t launch_shd_screen(const float4* prim_sp, uint32_t n, const float e[6], double delta,
+                             float2* out8, uint32_t* rr_max, hipStream_t st);
+hipError_t launch_albedo_refs(const uint32_t* prim_idx, const uint32_t* albedo, uint32_t n,
+                              uint32_t n_spheres, uint32_t* out, hipStream_t st);
+hipError_t launch_cam8_screen(const float4* prim_sp, uint32_t n, const float o[3], const float B[9],
+                              uint32_t ok, float2* out, hipStream_t st);
+// rt_query.hip: n rays (rt_ray) -> n hits (rt_hit) against a.sc; counters != null: a stats launch
+hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32_t n, bool any,
+                        unsigned long long* counters, hipStream_t st);
+// rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
+hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
+                          unsigned long long* counters, hipStream_t st);
+
+// rt_last_error(NULL): the calling thread's last failure without a handle
+extern thread_local std::string g_last_error;
+int fail(rt_renderer* r, int code, const std::string& msg);
+int hip_fail(rt_renderer* r, hipError_t e, const char* what);
+
+#define RT_HIP(r, call)                                   \
+    do {                                                  \
+        hipError_t e_ = (call);                           \
+        if (e_ != hipSuccess) return hip_fail((r), e_, #call); \
+    } while (0)
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;  // elements
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+template <typename T>
+int ensure(rt_renderer* r, DevBuf<T>& b, size_t n) {
+    if (b.n >= n && b.p) return RT_OK;
+    b.release();
+    if (n == 0) n = 1;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T));
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return hip_fail(r, e, "hipMalloc");
+    }
+    b.n = n;
+    return RT_OK;
+}
+
+// A device array derived from the scene's leaf references and a key of up to
+// 13 floats (a camera origin, a basis): its records stand for the scene
+// generation and the key they were made for.  query() sizes the array and says
+// whether the records must be remade (a reallocation forgets what they were
+// made for); commit() follows the kernel that remade them.
+template <typename T>
+struct DerivedRecords {
+    DevBuf<T> buf;
+    uint64_t gen = ~0ull;  // no scene yet
+    float key[13] = {};
+    int query(rt_renderer* r, size_t n, uint64_t scene_gen, const float* k, size_t nk, bool* stale) {
+        const T* before = buf.p;
+        if (const int st = ensure(r, buf, n)) return st;
+        if (buf.p != before) gen = ~0ull;
+        *stale = gen != scene_gen || (nk && memcmp(key, k, nk * sizeof(float)) != 0);
+        return RT_OK;
+    }
+    void commit(uint64_t scene_gen, const float* k, size_t nk) {
+        if (nk) memcpy(key, k, nk * sizeof(float));
+        gen = scene_gen;
+    }
+};
+
+// rt_create_multi: the frame's tiles over several
+// devices of this process; `r` (the handle) is devices[0]'s renderer
+struct MultiState {
+    static constexpr int F = 2;            // frames in flight
+    static constexpr uint32_t kTs = 64;    // tile side
+    std::vector<int> devs;                 // devs[0] = the handle's device
+    std::vector<rt_renderer*> peers;       // peers[k] renders device k's tiles (peers[0] = the handle)
+    uint32_t transport = 0;                // RT_TRANSPORT_RCCL / RT_TRANSPORT_PEER
+    std::vector<ncclComm*> comms;          // one per device (ncclCommInitAll)
+    std::vector<hipStream_t> cs;           // per-device comm stream
+    // devices[0]'s output stream: what a NULL stream argument means for the
+    // handle (rt_stream).  Not devices[0]'s render stream, so that the wait
+    // for frame j's unpack does not hold frame j+1's tiles on device 0.
+    hipStream_t out = nullptr;
+    // per frame slot f: each device's packed slab, devices[0]'s receive buffer
+    // of n slabs end to end, and the events that order their reuse (all
+    // timing-disabled: they are waited on every frame)
+    std::vector<void*> slab[F];
+    void* recv[F] = {nullptr, nullptr};
+    std::vector<hipEvent_t> rendered[F], sent[F];
+    hipEvent_t recvd[F] = {nullptr, nullptr}, unpacked[F] = {nullptr, nullptr}, out_ready = nullptr;
+    bool used[F] = {false, false};
+    // rt_get_multi_timing: timing events, recorded only once the caller has
+    // asked for timing: device k's render start / end, devices[0]'s
+    // unpack end; timed[f] = slot f's frame recorded them
+    bool timing = false;
+    bool timed[F] = {false, false};
+    std::vector<hipEvent_t> t_start[F], t_end[F];
+    hipEvent_t t_unpacked[F] = {nullptr, nullptr};
+    uint64_t frame = 0;
+    // a resize that failed part-way leaves the devices at different sizes:
+    // rt_render refuses the handle until a resize succeeds
+    bool broken = false;
+    // test-only fault injection (RT_TEST_FAULT with RT_FLAG_TEST_HOOKS, read
+    // once by rt_create_multi): "create:k" peer k's rt_create fails, "comm"
+    // ncclCommInitAll fails, "slab:k" the slab allocation on peer k fails,
+    // "queue:k" peer k's plain frames report themselves incomplete (as a
+    // slot that was never published: RendererState::test_fault_queue)
+    enum Fault { kNone = 0, kCreate, kComm, kSlab, kQueue };
+    int fault = kNone;
+    uint32_t fault_k = 0;
+    // tile plan for the current size
+    uint32_t W = 0, H = 0, S = 0;          // S = slab tiles
+    size_t slab_bytes = 0;
+    std::vector<std::vector<uint32_t>> ids;
+    std::vector<uint32_t> all_ids;         // n * S, padding slots RT_TILE_SKIP
+    uint32_t* d_all_ids = nullptr;         // on devices[0]
+};
+
+// what an rt_renderer holds (the C-ABI's opaque struct, below, is exactly this)
+struct RendererState {
+    rt_config cfg;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // completion of the renderer's last queued work (render, tiles, unpack) on
+    // whichever stream it ran: a launch on another stream is ordered after it
+    // (the counters, queue heads and buffers are shared), and
+    // rt_synchronize / rt_readback wait for it
+    hipEvent_t done = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool pending = false;
+    // wave-queue failure report (FrameArgs::qerr): a pinned host-coherent word
+    // the kernel stores a failed frame's id into; the host reports each new
+    // value once (queue_report), from rt_render without any copy or sync
+    uint32_t* qerr_host = nullptr;
+    uint32_t* qerr_dev = nullptr;
+    uint32_t frame_seq = 0;   // last frame id handed out (never 0)
+    uint32_t qerr_seen = 0;   // last reported value of *qerr_host
+    // test only (RT_TEST_FAULT=queue:k, RT_FLAG_TEST_HOOKS): plain frames
+    // report themselves failed
+    bool test_fault_queue = false;
+    float pose[16];
+    float K[9];
+    uint32_t W = 0, H = 0;
+    DevBuf<uint32_t> fb;
+    DevBuf<float4> rad;
+    DevBuf<float4> accum;            // RT_FLAG_PROGRESSIVE running sums
+    uint32_t frames_accum = 0;       // frames in `accum` (0: next frame starts over)
+    uint64_t accum_sig = 0;          // which pixels the sums belong to (frame / tile list)
+    DevBuf<unsigned long long> counters;
+    // the counters, queue heads and slot table in two sets of ctr_stride
+    // words: a scene frame uses set ctr_set and its kernel zeroes the other
+    // one for the next frame (FrameArgs::ctr_next), so no memset launch sits
+    // between frames; ctr_zero[s] = leading words of set s known to be zero
+    size_t ctr_stride = 0;
+    uint32_t ctr_set = 0;
+    size_t ctr_zero[2] = {0, 0};
+    // superblock claim order of full frames (FrameArgs::sb_order) and the
+    // superblock grid it was made for
+    DevBuf<uint32_t> sb_order;
+    uint32_t sb_nx = 0, sb_ny = 0;
+    // device copies of recently used tile lists (rt_render_tiles: this rank's
+    // list; rt_unpack_tiles on rank 0: one list per peer), least recently used
+    // evicted; each host vector stays alive as the source of its async upload
+    struct TileList {
+        std::vector<uint32_t> host;
+        DevBuf<uint32_t> dev;
+        uint64_t used = 0;
+    };
+    std::vector<TileList> tile_lists;
+    uint64_t tile_clock = 0;
+    // display buffer mapped per frame: the Displayer's
+    // registered GL PBO through the HIP graphics ops, or a caller's ops
+    rt_display_ops disp{};
+    void* disp_user = nullptr;
+    bool gl_disp = false;  // disp are the built-in HIP graphics-interop ops
+    // scene: the sphere list lives in d_spheres/d_albedo; `spheres` is a host
+    // copy when the scene came from host memory (host builder input)
+    uint32_t n_spheres = 0;
+    std::vector<float> spheres;
+    bool host_copy = false;
+    // leaf-reference arrays' length (prim_sp / prim_idx / the screen records):
+    // info.n_prim_refs, plus the gaps of the line-packed layout (pack_leaf_lines)
+    uint32_t prim_slots = 0;
+    bool leaf_packed = false;
+    // test only: RT_TEST_CLAIM_DELAY at rt_create with RT_FLAG_TEST_HOOKS
+    // (FrameArgs::wq_claim_delay)
+    uint32_t test_claim_delay = 0;
+    // test only, read at rt_create with RT_FLAG_TEST_HOOKS: the A/B switches
+    // RT_SORT=0 (no sorted rounds), RT_LDS_STAGE=0 (no LDS leaf staging),
+    // RT_LEAF_PACK=1 (line-packed leaf lists) and RT_SB_ORDER=1 (superblocks
+    // claimed along a Hilbert curve); images and counters are the same
+    bool sort_rounds = true, lds_stage = true, leaf_pack = false, sb_hilbert = false;
+    rt_octree_params oct;
+    bool has_scene = false;
+    GpuOctreeBuilder gpu_build;
+    CellTable cell_table;
+    DevBuf<uint2> d_nodes;
+    DevBuf<float4> d_prim_sp;
+    DevBuf<uint32_t> d_prim_idx;
+    DevBuf<float4> d_spheres;
+    DevBuf<uint32_t> d_albedo;
+    SceneArgs sc{};
+    uint64_t scene_gen = 0;  // counts scene builds: what the derived records are made for
+    // camera-relative screen records (SceneArgs::prim_cam); key: the camera origin
+    DerivedRecords<float4> prim_cam;
+    // image-plane screen records (SceneArgs::prim_cam8); key: the camera
+    // origin, the basis and its check (cam8_basis)
+    DerivedRecords<float2> prim_cam8;
+    // the light-plane screen records, {u, v} in 8 bytes (SceneArgs::prim_shd8;
+    // key: the basis), and their radius term (FrameArgs::shd_rr; d_shd_rr: the
+    // kernel's max, in bits, copied into shd_rr_bits)
+    DerivedRecords<float2> prim_shd8;
+    DevBuf<uint32_t> d_shd_rr;
+    uint32_t shd_rr_bits = 0;
+    float shd_rr = 0.0f;
+    // albedo by leaf reference (SceneArgs::prim_al); no key
+    DerivedRecords<uint32_t> prim_al;
+    // occluder lists (SceneArgs::prim_occ / occ_sp, occluder.hip): built with
+    // the light-plane records, for the same scene and light; occ_cap: the
+    // per-sphere cap (kOccCap, or RT_TEST_OCC_CAP under RT_FLAG_TEST_HOOKS);
+    // occ_e0 / occ_e1 time the build (collected at the renderer's next
+    // synchronisation, occ_collect_time); occ_M: the M the lists were made with
+    OccluderLists occ;
+    uint32_t occ_cap = kOccCap;
+    double occ_mean_max = kOccMeanMax;  // (RT_TEST_OCC_MEAN under RT_FLAG_TEST_HOOKS)
+    hipEvent_t occ_e0 = nullptr, occ_e1 = nullptr;
+    bool occ_timed = false;
+    double occ_M = 0.0;
+    // ray queries (rt_trace_rays, rt_pick): their own stat lines (a query never
+    // touches the frames' counter sets) and rt_pick's one ray and one hit
+    DevBuf<unsigned long long> q_counters;
+    DevBuf<float4> q_ray;
+    DevBuf<uint2> q_hit;
+    rt_scene_info info{};
+    std::string err;
+    // multi-device handle (rt_create_multi): this renderer is devices[0]'s
+    // part; the state holds the other devices' renderers and the transport
+    MultiState* multi = nullptr;
+    // the occluder lists stand for the current scene (made with its light-plane records)
+    bool occluders_current() const { return occ.on() && prim_shd8.gen == scene_gen; }
+};
+
+}  // namespace rtamd
+
+struct rt_renderer : rtamd::RendererState {};
+
+namespace rtamd {
+
+// rt_capi.cpp
+int set_device(rt_renderer* r);
+void fill_camera(const rt_renderer* r, CamArgs& cam);
+const char* test_env(uint32_t flags, const char* name);
+int order_after_last(rt_renderer* r, hipStream_t st);
+int mark_queued(rt_renderer* r, hipStream_t st);
+int queue_report(rt_renderer* r);
+void occ_collect_time(rt_renderer* r);
+// rt_scene.cpp
+int build_scene(rt_renderer* r);
+// rt_frame.cpp
+void fill_frame_args(rt_renderer* r, FrameArgs& a);
+int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats);
+int ensure_prim_al(rt_renderer* r, SceneArgs& sc, hipStream_t st);
+int check_tiles(rt_renderer* r, const uint32_t* ids, uint32_t n_tiles, uint32_t ts,
+                bool allow_skip = false);
+int tile_list(rt_renderer* r, const uint32_t* ids, uint32_t n, hipStream_t s, const uint32_t** out);
+void accum_pixels(rt_renderer* r, const uint32_t* ids, uint32_t n, uint32_t ts);
+int render_tiles_one(rt_renderer* r, const uint32_t* tile_ids, uint32_t n_tiles, uint32_t ts,
+                     void* dev_packed, void* stream, rt_stats* stats);
+int unpack_tiles_one(rt_renderer* r, const void* dev_packed, const uint32_t* tile_ids,
+                     uint32_t n_tiles, uint32_t ts, void* dev_rgba8, void* stream);
+// rt_multi.cpp: a multi-device handle's part of the calls above
+int multi_render(rt_renderer* r, uint32_t* out, hipStream_t hs, rt_stats* stats);
+int multi_wait(rt_renderer* r);
+int multi_synchronize(rt_renderer* r);
+int multi_queue_report(rt_renderer* r);
+void multi_destroy(rt_renderer* r);
+int multi_set_scene_device(rt_renderer* r, uint32_t n, const rt_octree_params* oct);
+
+// " (device <ordinal>, peer <k>)": names the device in a multi-device error
+inline std::string peer_name(const MultiState& m, size_t k) {
+    return " (device " + std::to_string(m.devs[k]) + ", peer " + std::to_string(k) + ")";
+}
+// apply `fn` to every other device's renderer of a multi-device handle
+template <typename Fn>
+int for_peers(rt_renderer* r, Fn fn) {
+    if (!r || !r->multi) return RT_OK;
+    for (size_t k = 1; k < r->multi->peers.size(); ++k) {
+        const int st = fn(r->multi->peers[k]);
+        if (st) {
+            r->err = r->multi->peers[k]->err + peer_name(*r->multi, k);
+            return st;
+        }
+    }
+    return RT_OK;
+}
+// the stream a NULL stream argument means: the renderer's own, or a
+// multi-device handle's output stream on devices[0]
+inline hipStream_t own_stream(const rt_renderer* r) { return r->multi ? r->multi->out : r->stream; }
+
+}  // namespace rtamd

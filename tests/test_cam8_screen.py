@@ -3,7 +3,7 @@ round 6 "An 8-byte image-plane screen for primary rays").
 
 With this screen a primary ray's chunk runs the exact ray-sphere tests only when
 the lane's image-plane point s = (Bd).xy / (Bd).z lies within rho of the
-sphere centre's projection q, both in the frame's basis B (rt_capi.cpp
+sphere centre's projection q, both in the frame's basis B (rt_frame_math.h
 cam8_basis), rho^2 stored as bf16 in the low bytes of the 8-byte record
 {qx, qy} (cam8_screen_kernel).  rho bounds |q_a - q_b| <= sin(theta) /
 (a_z cos(beta + theta)) for every direction within theta of the centre's,

@@ -115,7 +115,7 @@ SLACK_M, GROW = 64.0, 4.0  # rt_params.h kShadowSlackM; shd_screen_kernel's r (1
 
 
 def _kernel_light(ld):
-    """FrameArgs::L as rt_capi.cpp fill_frame_args makes it: -(ld / |ld|) in f32."""
+    """FrameArgs::L as rt_frame.cpp fill_frame_args makes it: -(ld / |ld|) in f32."""
     ld = np.asarray(ld, np.float32)
     ll = np.sqrt((ld[0] * ld[0] + ld[1] * ld[1]) + ld[2] * ld[2])
     return (-(ld / ll)).astype(np.float32)

@@ -21,6 +21,8 @@ import raytracingstudy_amd as rt
 from raytracingstudy_amd._lib import RtError
 from raytracingstudy_amd.camera import scene_pose
 
+from light_basis import kernel_light as _kernel_light
+
 pytestmark = pytest.mark.gpu
 
 U24 = 1.0 / 16777216.0
@@ -68,22 +70,6 @@ def _renderer(scene, w=96, h=64, spp=8, light=LIGHT, pose=None, **kw):
     r.setPosition(scene_pose() if pose is None else pose)
     r.set_scene(sp, al)
     return r
-
-
-def _kernel_light(ld):
-    """FrameArgs::L and the light-plane basis, as rt_capi.cpp makes them."""
-    ld = np.asarray(ld, np.float32)
-    ll = np.sqrt(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2], dtype=np.float32)
-    L = (-(ld / ll)).astype(np.float32)
-    l = L.astype(np.float64)
-    l /= np.linalg.norm(l)
-    k = int(np.argmin(np.abs(l)))      # first of the smallest, like the host loop
-    e1 = np.zeros(3)
-    e1[k] = 1.0
-    e1 -= l[k] * l
-    e1 /= np.linalg.norm(e1)
-    e2 = np.cross(l, e1)
-    return L, e1.astype(np.float32).astype(np.float64), e2.astype(np.float32).astype(np.float64)
 
 
 def _rule(sp, info, ld, slack, shrink=1.0):

@@ -3,7 +3,7 @@ images and counters whatever the padding after the last leaf list holds.
 
 The leaf loads read one sphere past a leaf's end, which for the last leaf is
 the kPrimPad tail (rt_params.h); its discriminant joins the leaf screen
-unmasked (rt_kernels.hip, walk<> leaf).  rt_capi.cpp fills the tail; the
+unmasked (rt_kernels.hip, walk<> leaf).  rt_scene.cpp fills the tail; the
 test-only pad_fill modes put NaN spheres or spheres covering the root box
 there, which pass the screen and force the exact path.  Round 2's driver run
 failed on case n5_100x70_s3_d7 of a since-removed variant (15, scalar leaf
