@@ -101,7 +101,9 @@ enum {
      * covering the root box.  Images and counters are the same for all three. */
     RT_FLAG_PAD_FILL_SHIFT = 8,
     /* Test-only: rt_create / rt_create_multi honour the RT_TEST_* environment
-     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY, RT_TEST_OCC_CAP, RT_TEST_OCC_MEAN)
+     * variables (RT_TEST_FAULT fault injection, RT_TEST_CLAIM_DELAY, RT_TEST_OCC_CAP, RT_TEST_OCC_MEAN,
+     * RT_TEST_BIN_CAP, RT_TEST_BIN_CAPACITY, RT_TEST_BIN_SHRINK, RT_TEST_BIN_MIN_SAMPLES,
+     * RT_TEST_BIN_MEAN)
      * and the A/B switches RT_SORT, RT_LDS_STAGE, RT_LEAF_PACK and RT_SB_ORDER
      * (none changes an image); without this flag they are
      * ignored (a set one is named on stderr once). */
@@ -115,6 +117,9 @@ enum {
      * round 7).  Images and counters are the same either way.  (Its own bit:
      * the eight RT_FLAG_OPT_SHIFT bits are all taken.) */
     RT_FLAG_NO_OCCLUDERS = 1u << 12,
+    /* A/B: no screen-space bins, every primary ray walks the octree (DESIGN.md
+     * 5.1 round 10).  Images and counters are the same either way. */
+    RT_FLAG_NO_BINS = 1u << 13,
     /* bits 16..19: scene-kernel variant for A/B runs (0 = default: 13, the
      * per-wave queue, for spp >= 8, else 7; others in DESIGN.md 5.1); images
      * and counters are identical across variants (packets: images only) */
@@ -248,6 +253,46 @@ int rt_export_octree(rt_renderer* r, uint32_t* nodes_out, float* prim_sp_out,
  * reference.  Any may be NULL. */
 int rt_export_occluders(rt_renderer* r, uint32_t* offsets_out, uint32_t* counts_out,
                         uint32_t* indices_out, uint32_t* prim_occ_out);
+/* Screen-space bins: every plain scene frame of the
+ * wave queue lists, per 8x8-pixel bin, the spheres its primary rays can meet,
+ * and answers those rays from the lists; the lists are rebuilt inside every
+ * such frame (the camera may move every frame).  rt_get_bin_info reports the
+ * handle's last frame (it waits for the handle's queued work). */
+enum {
+    RT_BINS_ON = 0,           /* the frame's primary rays were answered from the bins       */
+    RT_BINS_OFF_FLAG = 1,     /* RT_FLAG_NO_BINS                                             */
+    RT_BINS_OFF_KERNEL = 2,   /* a frame that walks by design: a stats frame, a block-tile
+                                 variant, a frame below the size at which bins pay, compat   */
+    RT_BINS_OFF_CAMERA = 3,   /* a pose that is not a rotation, or a degenerate intrinsic    */
+    RT_BINS_OFF_CAPACITY = 4, /* the entries did not fit the buffer: this frame walked, the
+                                 next one gets a larger buffer                               */
+    RT_BINS_OFF_WIDE = 5,     /* too many spheres around or beside the camera                */
+    RT_BINS_OFF_DENSE = 6,    /* mean list length over the rule's: the frame walked          */
+    RT_BINS_NO_FRAME = 7      /* nothing rendered yet                                        */
+};
+typedef struct rt_bin_info {
+    uint32_t enabled;         /* 1: reason == RT_BINS_ON                                     */
+    uint32_t reason;          /* RT_BINS_*                                                   */
+    uint32_t bin_size;        /* bin side in pixels (8)                                      */
+    uint32_t bins;            /* bins of the frame: ceil(W / 8) * ceil(H / 8)                */
+    uint32_t entries;         /* total length of the lists (what the frame needed)           */
+    uint32_t capacity;        /* entries the buffer held for that frame                      */
+    uint32_t non_empty_bins;
+    uint32_t longest;         /* the longest list                                            */
+    uint32_t overflowed_bins; /* bins over the per-bin cap: their pixels walked              */
+    uint32_t wide;            /* spheres in the frame-level list every pixel tests           */
+    float bin_build_ms;       /* device time of the frame's bin build; its events are
+                                 recorded only from the first rt_get_bin_info call on,
+                                 so 0 for frames queued before it                            */
+} rt_bin_info;
+int rt_get_bin_info(rt_renderer* r, rt_bin_info* info);
+/* Copy the last frame's bins to host memory (sizes from rt_get_bin_info;
+ * RT_E_STATE unless that frame built lists): headers_out 2*bins words, bin
+ * b = by * ceil(W/8) + bx: {first entry, count}, a count of 0xFFFFFFFF: the
+ * bin is over the cap and its pixels walk (its entries are still there, up to
+ * the next bin's first entry); indices_out `entries` sphere indices;
+ * wide_out `wide` sphere indices.  Any may be NULL. */
+int rt_export_bins(rt_renderer* r, uint32_t* headers_out, uint32_t* indices_out, uint32_t* wide_out);
 /* Synthetic scene generator: splitmix64 -> PCG32 from `seed`;
  * centres U[0,1.28)^3, radius 0.02*(1000/n)^(1/3)*U[0.5,1), albedo U[0.2,1). */
 int rt_generate_spheres(uint32_t n, uint32_t seed, float* spheres_out, uint32_t* albedo_out);

@@ -39,6 +39,7 @@ RT_FLAG_PAD_FILL_SHIFT = 8  # test-only: 0 zeros, 1 NaN, 2 covering spheres afte
 RT_FLAG_TEST_HOOKS = 1 << 10   # test-only: honour the RT_TEST_* environment variables
 RT_FLAG_TEST_POISON = 1 << 11  # test-only: sentinel-fill every frame's outputs first
 RT_FLAG_NO_OCCLUDERS = 1 << 12  # A/B: every shadow ray walks the octree (no occluder lists)
+RT_FLAG_NO_BINS = 1 << 13  # A/B: every primary ray walks the octree (no screen-space bins)
 RT_FLAG_VARIANT_SHIFT = 16
 RT_FLAG_OPT_SHIFT = 20
 RT_FLAG_CELL_TABLE_SHIFT = 28
@@ -125,6 +126,31 @@ class RtSceneInfo(ctypes.Structure):
         return d
 
 
+# rt_bin_info.reason
+RT_BINS_REASONS = ("on", "flag", "kernel", "camera", "capacity", "wide", "dense", "no_frame")
+
+
+class RtBinInfo(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_uint32),
+        ("reason", ctypes.c_uint32),
+        ("bin_size", ctypes.c_uint32),
+        ("bins", ctypes.c_uint32),
+        ("entries", ctypes.c_uint32),
+        ("capacity", ctypes.c_uint32),
+        ("non_empty_bins", ctypes.c_uint32),
+        ("longest", ctypes.c_uint32),
+        ("overflowed_bins", ctypes.c_uint32),
+        ("wide", ctypes.c_uint32),
+        ("bin_build_ms", ctypes.c_float),
+    ]
+
+    def as_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["reason"] = RT_BINS_REASONS[self.reason] if self.reason < len(RT_BINS_REASONS) else "?"
+        return d
+
+
 # rt_display_ops: int map(void* user, void* stream, void** ptr, size_t* bytes),
 # int unmap(void* user, void* stream)
 DISPLAY_MAP = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -206,6 +232,8 @@ SIGNATURES = {
     "rt_get_scene_info": (_int, [_P, ctypes.POINTER(RtSceneInfo)]),
     "rt_export_octree": (_int, [_P, _P, _P, _P]),
     "rt_export_occluders": (_int, [_P, _P, _P, _P, _P]),
+    "rt_get_bin_info": (_int, [_P, ctypes.POINTER(RtBinInfo)]),
+    "rt_export_bins": (_int, [_P, _P, _P, _P]),
     "rt_save_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32]),
     "rt_load_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32, ctypes.POINTER(_u32)]),
     "rt_generate_spheres": (_int, [_u32, _u32, _P, _P]),
@@ -240,7 +268,8 @@ test_flags = 0
 
 # the sources the scene kernel's machine code is built from (device code and
 # its compile flags): a PMC summary is valid for a build iff its stamp matches
-KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_params.h", "csrc/Makefile")
+KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_bins.h", "csrc/rt_bins_math.h",
+                  "csrc/screen_bins.hip", "csrc/rt_params.h", "csrc/Makefile")
 
 
 def kernel_source_id() -> str:

@@ -1,0 +1,146 @@
+// rt_bins_math.h — the screen-space bins' per-sphere arithmetic (DESIGN.md 5.1
+// round 10), free of HIP and of the renderer's state: plain arrays in and out,
+// f64 operations in a fixed order (built with -ffp-contract=off like the
+// rest).  screen_bins.hip runs it per sphere on the device, and
+// tests/native/bins_math_dump.cpp prints it for tests/test_bins_cpu.py on the CPU.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define RT_BINS_HD __host__ __device__
+#else
+#define RT_BINS_HD
+#endif
+
+namespace rtamd {
+
+// Bin side: 2^kBinShift pixels.  Every wave tile (1x1 .. 8x8 pixels, aligned)
+// lies in one bin, so a wave reads one list whatever the spp.
+constexpr uint32_t kBinShift = 3;
+constexpr uint32_t kBinSide = 1u << kBinShift;
+// A bin with more entries than this walks (its header count is kBinWalk): one
+// wave sorts a list, a lane an entry.
+constexpr uint32_t kBinCap = 64;
+constexpr uint32_t kBinWalk = 0xFFFFFFFFu;
+// The frame-level list of spheres every pixel tests (camera inside, or the
+// sphere straddles the camera plane); more of them: the frame walks.
+constexpr uint32_t kBinWideCap = 32;
+// A frame whose non-empty bins hold more than this many entries on average
+// walks (a device-side rule, screen_bins.hip: bins_decide_kernel): past it
+// most bins are over kBinCap anyway and the fill is work for nothing.
+constexpr uint32_t kBinMeanMax = 48;
+// After a frame the rule above sent walking, the next kBinDenseSkip plain
+// frames build no bins at all (they run the instances without them), then one
+// probes again: a dense scene pays the count pass once in 16 frames (C5: 0.65
+// ms a frame otherwise, profiles/r10).  Read from the pinned info words
+// without a sync; whatever it decides, a frame's pixels are the same.
+constexpr uint32_t kBinDenseSkip = 15;
+// Frames of fewer primary samples than this walk: the build is seven short
+// launches (75 us on C2's 1,000 spheres), more than such a frame's whole
+// kernel (C2, 2.07 M samples: 0.093 ms walking, 0.170 ms with bins).
+constexpr uint64_t kBinMinSamples = 1ull << 22;
+
+// Slack of the rectangle and the near bound.  A ray
+// isect accepts passes within r (1 + 2.5 u) + 20 u D of the centre, D = |c - o|
+// (isect's b, q and h roundings: 8 u D; the f32 ray direction against the
+// exact pinhole ray through the sample: 12 u D), and a pose whose rotation is
+// orthonormal to 2^-20 (the host's gate, bins_camera_ok) moves the centre's
+// camera coordinates by at most 2 * 2^-20 D.  r'' = r (1 + 1e-6) + 2^-17 D
+// holds both: 2^-17 = 64 u + 4 * 2^-20.
+constexpr double kBinSlackDist = 1.0 / 131072.0;
+// the sample's image coordinate x + jitter is rounded to f32: at most
+// 2^-24 * 32768 pixels, and (u - K2) / K0 adds 2 u relative; 1/64 pixel and
+// 1e-6 relative hold both
+constexpr double kBinSlackPix = 1.0 / 64.0;
+constexpr double kBinSlackPixRel = 1e-6;
+constexpr double kBinOrthoGate = 1.0 / 1048576.0;  // 2^-20
+
+enum BinClass : uint32_t { kBinDropped = 0, kBinBinned = 1, kBinWide = 2 };
+
+struct BinRect {
+    uint32_t cls;            // BinClass
+    uint32_t x0, y0, x1, y1; // pixels, inclusive, clipped to the image (binned only)
+    float near_t;            // a lower bound on every t isect can accept (>= 0)
+};
+
+// Whether a frame of this camera may use bins: K's focal terms finite and
+// non-zero and R orthonormal to kBinOrthoGate (the slack above assumes it).
+RT_BINS_HD inline bool bins_camera_ok(const float K[9], const float R[9], const float o[3]) {
+    for (int i = 0; i < 3; ++i)
+        if (!isfinite(static_cast<double>(o[i]))) return false;
+    const double k0 = K[0], k4 = K[4], k2 = K[2], k5 = K[5];
+    if (!isfinite(k0) || !isfinite(k4) || !isfinite(k2) || !isfinite(k5) || k0 == 0.0 || k4 == 0.0) return false;
+    for (int a = 0; a < 3; ++a)
+        for (int b = a; b < 3; ++b) {
+            double s = 0.0;
+            for (int i = 0; i < 3; ++i) s += static_cast<double>(R[3 * a + i]) * R[3 * b + i];
+            if (!(fabs(s - (a == b ? 1.0 : 0.0)) <= kBinOrthoGate)) return false;
+        }
+    return true;
+}
+
+// The pixels whose samples may meet sphere sp = {cx, cy, cz, r} (radius scaled
+// by `shrink`: 1 in the product, 0.9 under the negative-control test hook) for
+// the camera getRay uses (K[c*3+r], R = mat3(pose) column-major, origin o) on
+// a W x H image, and the near bound.
+//  * camera coordinates {X, Y, Z} = R^T (c - o): a sample's ray is along
+//    {dx, dy, 1} there, dx = (u - K[2]) / K[0];
+//  * wholly behind the camera plane (Z < -r''): dropped, every ray has z > 0;
+//  * the camera within r'' (1 + 1e-4) of the centre, or the sphere reaching
+//    the camera plane (Z <= r''), or a non-finite term: wide;
+//  * else per axis the tangent lines from the origin to the circle of radius
+//    r'' about {X, Z} in that axis' plane bound x / z:
+//    (X Z -+ r'' sqrt(X^2 + Z^2 - r''^2)) / (Z^2 - r''^2),
+//    mapped to pixels, widened by the slack, floored: pixel x holds samples
+//    u in [x, x + 1].
+RT_BINS_HD inline BinRect sphere_screen_rect(const float sp[4], const float K[9], const float R[9],
+                                             const float o[3], uint32_t W, uint32_t H, double shrink) {
+    BinRect out;
+    out.cls = kBinWide;
+    out.x0 = out.y0 = 0u;
+    out.x1 = W ? W - 1u : 0u;
+    out.y1 = H ? H - 1u : 0u;
+    out.near_t = 0.0f;
+    const double vx = static_cast<double>(sp[0]) - o[0], vy = static_cast<double>(sp[1]) - o[1],
+                 vz = static_cast<double>(sp[2]) - o[2];
+    const double X = static_cast<double>(R[0]) * vx + static_cast<double>(R[1]) * vy + static_cast<double>(R[2]) * vz;
+    const double Y = static_cast<double>(R[3]) * vx + static_cast<double>(R[4]) * vy + static_cast<double>(R[5]) * vz;
+    const double Z = static_cast<double>(R[6]) * vx + static_cast<double>(R[7]) * vy + static_cast<double>(R[8]) * vz;
+    const double dist = sqrt(vx * vx + vy * vy + vz * vz);
+    const double rp = static_cast<double>(sp[3]) * shrink * (1.0 + 1e-6) + kBinSlackDist * dist;
+    if (!isfinite(dist) || !isfinite(rp) || !(rp >= 0.0)) return out;
+    if (Z < -rp) {
+        out.cls = kBinDropped;
+        return out;
+    }
+    if (!(dist > rp * 1.0001) || !(Z > rp)) return out;
+    const double nb = (dist - rp) * (1.0 - kBinOrthoGate);
+    out.near_t = nb > 0.0 ? static_cast<float>(nb) : 0.0f;
+    double lo[2], hi[2];
+    const double C[2] = {X, Y};
+    const double kf[2] = {K[0], K[4]}, kc[2] = {K[2], K[5]};
+    const double den = Z * Z - rp * rp;
+    for (int a = 0; a < 2; ++a) {
+        const double s = rp * sqrt(C[a] * C[a] + den);
+        const double p0 = kf[a] * ((C[a] * Z - s) / den) + kc[a];
+        const double p1 = kf[a] * ((C[a] * Z + s) / den) + kc[a];
+        if (!isfinite(p0) || !isfinite(p1)) return out;
+        const double mn = p0 < p1 ? p0 : p1, mx = p0 < p1 ? p1 : p0;
+        lo[a] = floor(mn - kBinSlackPix - kBinSlackPixRel * fabs(mn));
+        hi[a] = floor(mx + kBinSlackPix + kBinSlackPixRel * fabs(mx));
+    }
+    const double wmax = static_cast<double>(W) - 1.0, hmax = static_cast<double>(H) - 1.0;
+    if (hi[0] < 0.0 || hi[1] < 0.0 || lo[0] > wmax || lo[1] > hmax) {
+        out.cls = kBinDropped;
+        return out;
+    }
+    out.cls = kBinBinned;
+    out.x0 = static_cast<uint32_t>(lo[0] > 0.0 ? lo[0] : 0.0);
+    out.y0 = static_cast<uint32_t>(lo[1] > 0.0 ? lo[1] : 0.0);
+    out.x1 = static_cast<uint32_t>(hi[0] < wmax ? hi[0] : wmax);
+    out.y1 = static_cast<uint32_t>(hi[1] < hmax ? hi[1] : hmax);
+    return out;
+}
+
+}  // namespace rtamd

@@ -185,6 +185,19 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
         r->occ_cap = static_cast<uint32_t>(std::min<unsigned long>(kOccCapMax, strtoul(oc, nullptr, 10)));
     // ... and the scene rule's mean candidate count (a dense test scene on lists)
     if (const char* om = test_env(cfg->flags, "RT_TEST_OCC_MEAN")) r->occ_mean_max = strtod(om, nullptr);
+    // test only (tests/test_gpu_bins.py): the per-bin cap of the screen-space
+    // bins, a tiny entry buffer (the frame-level fallback), rectangles from
+    // radii x 0.9 (a negative control: unsound lists), the frame size below
+    // which a frame walks
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_CAP"))
+        r->bin_cap = static_cast<uint32_t>(std::min<unsigned long>(64ul, strtoul(v, nullptr, 10)));
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_CAPACITY"))
+        r->bin_capacity_test = static_cast<uint32_t>(std::max(1ul, std::min(1ul << 24, strtoul(v, nullptr, 10))));
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_SHRINK")) r->bin_shrink = atoi(v) != 0 ? 0.9 : 1.0;
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_MIN_SAMPLES")) r->bin_min_samples = strtoull(v, nullptr, 10);
+    // ... and the mean list length over which a frame walks (tiny test frames are dense)
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_MEAN"))
+        r->bin_mean_max = static_cast<uint32_t>(std::min(1ul << 20, strtoul(v, nullptr, 10)));
     if (const char* fe = test_env(cfg->flags, "RT_TEST_FAULT"))
         r->test_fault_queue = strcmp(fe, "queue:0") == 0;
     // ... and the A/B switches ("0" off, any other number on)
@@ -212,6 +225,16 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
     if (e == hipSuccess) {
         *r->qerr_host = 0;
         e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->qerr_dev), r->qerr_host, 0);
+    }
+    // the screen-space bins' info words: pinned like the failure word
+    if (e == hipSuccess) e = hipEventCreate(&r->bin_e0);
+    if (e == hipSuccess) e = hipEventCreate(&r->bin_e1);
+    if (e == hipSuccess)
+        e = hipHostMalloc(reinterpret_cast<void**>(&r->bin_mirror), kBinInfoWords * sizeof(uint32_t),
+                          hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) {
+        memset(r->bin_mirror, 0, kBinInfoWords * sizeof(uint32_t));
+        e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->bin_mirror_dev), r->bin_mirror, 0);
     }
     if (e != hipSuccess) {
         st = hip_fail(nullptr, e, "rt_create");
@@ -258,6 +281,18 @@ int rt_destroy(rt_renderer* r) {
     r->gpu_build.release();
     r->cell_table.release();
     r->occ.release();
+    r->bin_first_ref.buf.release();
+    r->bin_rects.release();
+    r->bin_ent.release();
+    r->bin_wide.release();
+    r->bin_cnt.release();
+    r->bin_offs.release();
+    r->bin_info.release();
+    r->bin_hdr.release();
+    r->bin_temp.release();
+    if (r->bin_e0) (void)hipEventDestroy(r->bin_e0);
+    if (r->bin_e1) (void)hipEventDestroy(r->bin_e1);
+    if (r->bin_mirror) (void)hipHostFree(r->bin_mirror);
     if (r->occ_e0) (void)hipEventDestroy(r->occ_e0);
     if (r->occ_e1) (void)hipEventDestroy(r->occ_e1);
     if (r->ev0) (void)hipEventDestroy(r->ev0);

@@ -1,6 +1,7 @@
 // rt_frame.cpp — what a renderer queues per call: a frame's preparation and
 // launch (do_render and its steps), tile frames, ray queries, the G-buffer.
 // The arithmetic the images depend on is rt_frame_math.h's.
+#include "rt_bins_math.h"
 #include "rt_frame_math.h"
 #include "rt_host.h"
 
@@ -327,6 +328,120 @@ bool camera_in_occluder_gate(const rt_renderer* r, const FrameArgs& a) {
     return occ_camera_in_gate(a.cam.o, r->info.root_min, r->info.root_max, kOccCamGate * r->occ_M);
 }
 
+// Step 4b: this frame's screen-space bins (screen_bins.hip, DESIGN.md 5.1
+// round 10), queued on `st` ahead of the frame kernel: built by every plain
+// frame whose kernel reads them, never keyed on the pose (the Displayer's
+// camera moves every frame), with no wait and no readback.  The buffer sizes
+// are fixed here; a frame whose entries do not fit sets its device flag and
+// walks, the flag lands in the renderer's pinned words, and the next frame
+// that sees it grows the buffer.
+int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
+    a.bin_hdr = nullptr;
+    a.bin_ent = nullptr;
+    a.bin_wide = nullptr;
+    a.bin_info = nullptr;
+    a.bin_nbx = 0;
+    r->bin_timed = false;
+    if (r->cfg.flags & RT_FLAG_NO_BINS) return r->bin_last_reason = RT_BINS_OFF_FLAG, RT_OK;
+    if (a.count_work || !frame_reads_bins(a, r->sort_rounds) ||
+        static_cast<uint64_t>(a.W) * a.H * a.spp < r->bin_min_samples)
+        return r->bin_last_reason = RT_BINS_OFF_KERNEL, RT_OK;
+    float B[9];
+    if (!bins_camera_ok(a.cam.K, a.cam.R, a.cam.o) || !cam8_basis(a.cam.K, a.cam.R, a.W, a.H, B))
+        return r->bin_last_reason = RT_BINS_OFF_CAMERA, RT_OK;
+    // a scene the device rule found too dense: probe once in kBinDenseSkip + 1 frames
+    if (r->bin_skip_gen != r->scene_gen) r->bin_dense_skip = 0, r->bin_skip_gen = r->scene_gen;
+    if (!r->bin_dense_skip && r->bin_last_frame && r->bin_mirror[kBinInfoFrame] == r->bin_last_frame &&
+        r->bin_mirror[kBinInfoFlag] == kBinFlagDense) {
+        r->bin_dense_skip = kBinDenseSkip + 1u;
+        r->bin_last_frame = 0;  // (this observation is used up: the probe makes the next one)
+    }
+    if (r->bin_dense_skip) {
+        --r->bin_dense_skip;
+        return r->bin_last_reason = RT_BINS_OFF_DENSE, RT_OK;
+    }
+    int ost;
+    bool stale;
+    if ((ost = r->bin_first_ref.query(r, std::max(1u, r->n_spheres), r->scene_gen, nullptr, 0, &stale))) return ost;
+    if (stale) {
+        hipError_t e = launch_first_refs(a.sc.prim_sp, a.sc.prim_idx, r->prim_slots, r->d_spheres.p,
+                                         r->n_spheres, r->bin_first_ref.buf.p, st);
+        if (e != hipSuccess) return hip_fail(r, e, "screen bins (first references)");
+        r->bin_first_ref.commit(r->scene_gen, nullptr, 0);
+    }
+    const uint32_t nbx = (a.W + kBinSide - 1u) / kBinSide, nby = (a.H + kBinSide - 1u) / kBinSide;
+    const uint32_t nb = nbx * nby;
+    // the entry buffer: 6 per sphere to start with (C3 needs 3.1, C5 2.0), grown
+    // when the last frame that built bins reported that it did not fit
+    // (RT_TEST_BIN_CAPACITY: a tiny first buffer, so the first frame overflows)
+    size_t want = r->bin_capacity_test ? r->bin_capacity_test : 6ull * r->n_spheres + 65536ull;
+    if (r->bin_last_frame && r->bin_mirror[kBinInfoFrame] == r->bin_last_frame &&
+        (r->bin_mirror[kBinInfoFlag] & kBinFlagCapacity))
+        want = std::max<size_t>(want, size_t(r->bin_mirror[kBinInfoEntries]) + r->bin_mirror[kBinInfoEntries] / 4u);
+    want = std::min<size_t>(std::max<size_t>(want, r->bin_ent.n / 2), 0x7FFFFFFFull / 4u);
+    if (r->bin_ent.n < 2 * want) {
+        // (the buffer may still be read by a frame in flight on another stream)
+        if (r->bin_ent.p) RT_HIP(r, hipDeviceSynchronize());
+        if ((ost = ensure(r, r->bin_ent, 2 * want))) return ost;
+    }
+    if ((ost = ensure(r, r->bin_rects, std::max(1u, r->n_spheres))) ||
+        (ost = ensure(r, r->bin_cnt, 2ull * nb + 1ull)) || (ost = ensure(r, r->bin_offs, nb + 1ull)) ||
+        (ost = ensure(r, r->bin_hdr, nb)) || (ost = ensure(r, r->bin_wide, 2ull * kBinWideCap)) ||
+        (ost = ensure(r, r->bin_info, kBinInfoWords)))
+        return ost;
+    if (r->bin_temp_items < nb + 1u || !r->bin_temp.p) {
+        const size_t bytes = bins_scan_temp_bytes(nb + 1u);
+        if (!bytes) return fail(r, RT_E_HIP, "screen bins: scan scratch size");
+        if ((ost = ensure(r, r->bin_temp, bytes))) return ost;
+        r->bin_temp_items = nb + 1u;
+    }
+    BinBuild b{};
+    b.spheres = r->d_spheres.p;
+    b.first_ref = r->bin_first_ref.buf.p;
+    b.n_spheres = r->n_spheres;
+    memcpy(b.K, a.cam.K, sizeof(b.K));
+    memcpy(b.R, a.cam.R, sizeof(b.R));
+    memcpy(b.o, a.cam.o, sizeof(b.o));
+    b.W = a.W;
+    b.H = a.H;
+    b.nbx = nbx;
+    b.nby = nby;
+    b.shrink = r->bin_shrink;
+    b.capacity = static_cast<uint32_t>(r->bin_ent.n / 2);
+    b.cap = r->bin_cap;
+    b.mean_max = r->bin_mean_max;
+    b.frame_id = a.frame_id;
+    b.rects = r->bin_rects.p;
+    b.counts = r->bin_cnt.p;
+    b.cursor = r->bin_cnt.p + nb + 1u;
+    b.offs = r->bin_offs.p;
+    b.hdr = r->bin_hdr.p;
+    b.ent = r->bin_ent.p;
+    b.wide = r->bin_wide.p;
+    b.info = r->bin_info.p;
+    b.mirror = r->bin_mirror_dev;
+    b.temp = r->bin_temp.p;
+    b.temp_bytes = r->bin_temp.n;
+    if (r->bin_timing) RT_HIP(r, hipEventRecord(r->bin_e0, st));
+    hipError_t e = launch_screen_bins(b, st);
+    if (e != hipSuccess) return hip_fail(r, e, "screen bins");
+    if (r->bin_timing) {
+        RT_HIP(r, hipEventRecord(r->bin_e1, st));
+        r->bin_timed = true;
+    }
+    r->bin_last_reason = RT_BINS_ON;  // (the device flag may still send the frame walking: rt_get_bin_info)
+    r->bin_last_frame = a.frame_id;
+    r->bin_last_capacity = b.capacity;
+    r->bin_nbx = nbx;
+    r->bin_nby = nby;
+    a.bin_hdr = r->bin_hdr.p;
+    a.bin_ent = r->bin_ent.p;
+    a.bin_wide = r->bin_wide.p;
+    a.bin_info = r->bin_info.p;
+    a.bin_nbx = nbx;
+    return RT_OK;
+}
+
 // The two diagnostic builds, each a begin / end pair around the launch (empty in the product).
 #ifdef RT_TIMELINE
 // tools/timeline.sh: every frame appends its per-wave timeline to $RT_TIMELINE_FILE
@@ -441,6 +556,11 @@ int rtamd::do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats
     }
     if ((ost = poison_outputs(r, a, st))) return ost;
     a.count_work = stats ? 1u : 0u;
+    if (scene) {
+        if ((ost = screen_bins(r, a, st))) return ost;
+    } else {
+        r->bin_last_reason = RT_BINS_OFF_KERNEL;
+    }
     a.test_fault_queue = r->test_fault_queue && !stats ? 1u : 0u;
     if (stats) RT_HIP(r, hipEventRecord(r->ev0, st));
     if ((ost = launch_frame(r, a, st))) return ost;
@@ -534,6 +654,53 @@ int query_stats_read(rt_renderer* r, const unsigned long long* ctr, rt_stats* st
 }  // namespace
 
 extern "C" {
+
+int rt_get_bin_info(rt_renderer* r, rt_bin_info* info) {
+    if (!r || !info) return fail(r, RT_E_INVALID, "rt_get_bin_info: null argument");
+    if (const int st = rt_synchronize(r)) return st;
+    memset(info, 0, sizeof(*info));
+    info->bin_size = kBinSide;
+    info->reason = r->bin_last_reason;
+    if (r->bin_last_reason == RT_BINS_ON) {
+        const uint32_t* m = r->bin_mirror;
+        if (m[kBinInfoFrame] != r->bin_last_frame)
+            return fail(r, RT_E_STATE, "rt_get_bin_info: the last frame's bin words never arrived");
+        const uint32_t flag = m[kBinInfoFlag];
+        info->reason = flag & kBinFlagCapacity ? RT_BINS_OFF_CAPACITY
+                       : flag & kBinFlagWide   ? RT_BINS_OFF_WIDE
+                       : flag & kBinFlagDense  ? RT_BINS_OFF_DENSE
+                                               : RT_BINS_ON;
+        info->bins = r->bin_nbx * r->bin_nby;
+        info->entries = m[kBinInfoEntries];
+        info->capacity = r->bin_last_capacity;
+        info->non_empty_bins = m[kBinInfoNonEmpty];
+        info->longest = m[kBinInfoLongest];
+        info->overflowed_bins = m[kBinInfoOver];
+        info->wide = m[kBinInfoWide];
+        if (r->bin_timed) (void)hipEventElapsedTime(&info->bin_build_ms, r->bin_e0, r->bin_e1);
+    }
+    info->enabled = info->reason == RT_BINS_ON ? 1u : 0u;
+    r->bin_timing = true;  // frames record the build's events from now on
+    return RT_OK;
+}
+
+int rt_export_bins(rt_renderer* r, uint32_t* headers_out, uint32_t* indices_out, uint32_t* wide_out) {
+    rt_bin_info bi;
+    if (const int st = rt_get_bin_info(r, &bi)) return st;
+    if (!bi.enabled) return fail(r, RT_E_STATE, "rt_export_bins: the last frame built no lists");
+    if (headers_out && bi.bins)
+        RT_HIP(r, hipMemcpy(headers_out, r->bin_hdr.p, bi.bins * sizeof(uint2), hipMemcpyDeviceToHost));
+    std::vector<BinEntry> ent(std::max(bi.entries, bi.wide));
+    if (indices_out && bi.entries) {
+        RT_HIP(r, hipMemcpy(ent.data(), r->bin_ent.p, bi.entries * sizeof(BinEntry), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < bi.entries; ++i) indices_out[i] = ent[i].idx;
+    }
+    if (wide_out && bi.wide) {
+        RT_HIP(r, hipMemcpy(ent.data(), r->bin_wide.p, bi.wide * sizeof(BinEntry), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < bi.wide; ++i) wide_out[i] = ent[i].idx;
+    }
+    return RT_OK;
+}
 
 int rt_render_tiles(rt_renderer* r, const uint32_t* tile_ids, uint32_t n_tiles, uint32_t ts,
                     void* dev_packed, void* stream, rt_stats* stats) {

@@ -18,6 +18,7 @@
 
 #include "../../include/rt.h"
 #include "octree_gpu.h"
+#include "rt_bins_math.h"
 #include "rt_params.h"
 #include "scene_build.h"
 
@@ -46,6 +47,39 @@ hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
+
+// screen_bins.hip: the per-frame screen-space bins
+struct BinBuild {
+    const float4* spheres;      // by sphere index
+    const uint32_t* first_ref;  // per sphere: one leaf reference of it (launch_first_refs)
+    uint32_t n_spheres;
+    float K[9], R[9], o[3];     // the frame's camera (CamArgs)
+    uint32_t W, H, nbx, nby;
+    double shrink;              // 1; 0.9 under the test hook RT_TEST_BIN_SHRINK
+    uint32_t capacity;          // entries `ent` holds
+    uint32_t cap;               // a bin over it walks (<= kBinCap)
+    uint32_t mean_max;          // the frame walks over this mean list length
+    uint32_t frame_id;
+    uint4* rects;               // [n_spheres] scratch
+    uint32_t* counts;           // [nbx * nby + 1], then
+    uint32_t* cursor;           // [nbx * nby] in the same allocation
+    uint32_t* offs;             // [nbx * nby + 1]
+    uint2* hdr;                 // [nbx * nby]
+    uint4* ent;                 // [2 * capacity]
+    uint4* wide;                // [2 * kBinWideCap]
+    uint32_t* info;             // [kBinInfoWords]
+    uint32_t* mirror;           // the renderer's pinned copy of info (device pointer)
+    void* temp;                 // the scan's scratch
+    size_t temp_bytes;
+};
+hipError_t launch_first_refs(const float4* prim_sp, const uint32_t* prim_idx, uint32_t n_slots,
+                             const float4* spheres, uint32_t n_spheres, uint32_t* first_ref,
+                             hipStream_t st);
+size_t bins_scan_temp_bytes(uint32_t n_items);
+hipError_t launch_screen_bins(const BinBuild& b, hipStream_t st);
+// rt_kernels.hip: whether launch_scene would run this frame on an instance
+// that reads bins (the scene_kernel_w8 instances: plain frames of the wave queue)
+bool frame_reads_bins(const FrameArgs& a, bool sort);
 
 // rt_last_error(NULL): the calling thread's last failure without a handle
 extern thread_local std::string g_last_error;
@@ -266,6 +300,32 @@ struct RendererState {
     hipEvent_t occ_e0 = nullptr, occ_e1 = nullptr;
     bool occ_timed = false;
     double occ_M = 0.0;
+    // screen-space bins (screen_bins.hip), rebuilt by
+    // every plain frame that reads them.  bin_first_ref: per sphere, made once
+    // per scene.  bin_cnt: counts and cursors; bin_info / bin_mirror: the
+    // frame's info words on the device and their pinned host copy, which the
+    // next rt_render reads without a sync (a frame that overflowed bin_ent
+    // walks, and the next frame gets a larger buffer).  bin_cap /
+    // bin_capacity_test / bin_shrink / bin_min_samples / bin_mean_max: RT_TEST_BIN_* hooks.
+    DerivedRecords<uint32_t> bin_first_ref;
+    DevBuf<uint4> bin_rects, bin_ent, bin_wide;
+    DevBuf<uint32_t> bin_cnt, bin_offs, bin_info;
+    DevBuf<uint2> bin_hdr;
+    DevBuf<unsigned char> bin_temp;
+    uint32_t bin_temp_items = 0;
+    uint32_t* bin_mirror = nullptr;
+    uint32_t* bin_mirror_dev = nullptr;
+    uint32_t bin_cap = 64, bin_capacity_test = 0, bin_nbx = 0, bin_nby = 0;
+    double bin_shrink = 1.0;
+    uint64_t bin_min_samples = kBinMinSamples;
+    uint32_t bin_dense_skip = 0;    // plain frames still to run without a build (kBinDenseSkip)
+    uint64_t bin_skip_gen = 0;      // ... counted for this scene generation
+    uint32_t bin_mean_max = 48;     // kBinMeanMax (RT_TEST_BIN_MEAN)
+    uint32_t bin_last_reason = RT_BINS_NO_FRAME;   // RT_BINS_NO_FRAME
+    uint32_t bin_last_frame = 0;    // the frame id of the last frame that built bins
+    uint32_t bin_last_capacity = 0;
+    hipEvent_t bin_e0 = nullptr, bin_e1 = nullptr;
+    bool bin_timing = false, bin_timed = false;
     // ray queries (rt_trace_rays, rt_pick): their own stat lines (a query never
     // touches the frames' counter sets) and rt_pick's one ray and one hit
     DevBuf<unsigned long long> q_counters;

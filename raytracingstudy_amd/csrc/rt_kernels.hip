@@ -18,6 +18,7 @@
 
 #include "rt_params.h"
 #include "rt_walk.h"  // scene mode: the octree walk (shared with rt_query.hip)
+#include "rt_bins.h"  // scene mode: primary rays from the frame's screen-space bins
 
 namespace rtamd {
 
@@ -197,12 +198,17 @@ __device__ __forceinline__ uint32_t hit_albedo(SA& S, uint32_t h) {
 
 // Unified lane path: one walk instance run twice (primary, then the shadow ray
 // of the lanes that need one), so the register allocator sees one walk.
-template <int kChunk, bool kStats, bool kCam8 = false, bool kOcc = false>
+// kBin: the primary ray is answered from the frame's screen-space bins
+// (rt_bins.h; (tox, toy): the wave tile's origin pixel, wave-uniform); a tile
+// whose bin is over the cap, or a frame whose builder raised its flag, walks
+// under a wave-uniform branch.
+template <int kChunk, bool kStats, bool kCam8 = false, bool kOcc = false, bool kBin = false>
 __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uint32_t x,
                                                          uint32_t y, uint32_t hp, uint32_t s,
                                                          bool valid, uint32_t& n_shadow,
                                                          uint32_t& n_nodes, uint32_t& n_prims,
-                                                         void* stk, uint32_t* bs, uint32_t lbs) {
+                                                         void* stk, uint32_t* bs, uint32_t lbs,
+                                                         uint32_t tox = 0, uint32_t toy = 0) {
     const SceneArgs& S = a.sc;
     KernArgs* ka = kernargs();
     float u = static_cast<float>(x), v = static_cast<float>(y);
@@ -230,7 +236,15 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
         float t = 0.0f;
         uint32_t idx = 0;
         bool hit = false;
-        if (active) {
+        bool binned = false;
+        if (kBin && phase == 0) {
+            uint2 bh;
+            binned = !bin_header(tox, toy, bh);
+            if (binned)
+                hit = bin_nearest(bh, tox, toy, kernargs()->tw, kernargs()->th, active, r0, r1, r2, d0,
+                                  d1, d2, t, idx);
+        }
+        if (active && !binned) {
             RT_BS(kBsPhase);
             if (phase) RT_BS(kBsPhaseShadow);
             if (phase == 0)
@@ -303,7 +317,8 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
 // live across the walks instead of the slot and the tile-local origin).
 // Rounds of spw samples, pairwise butterfly per round, rounds added in
 // order in the leader's LDS slot, then the mean is written.
-template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kCam8 = false, bool kOcc = false>
+template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kCam8 = false, bool kOcc = false,
+          bool kBin = false>
 __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc, void* stk,
                                                 uint32_t ox, uint32_t oy, uint32_t obase,
                                                 uint32_t& n_primary,
@@ -330,8 +345,8 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
         const uint32_t sg = r * spw + sub_base;
         const bool valid = lane_ok && sg < s_end;
         n_primary += static_cast<uint32_t>(__popcll(__ballot(valid)));  // wave-uniform
-        PixelOut c = sample_color_unified<kChunk, kStats, kCam8, kOcc>(a, x, y, hp, sg, valid, n_shadow,
-                                                          n_nodes, n_prims, stk, bs, lbs);
+        PixelOut c = sample_color_unified<kChunk, kStats, kCam8, kOcc, kBin>(a, x, y, hp, sg, valid, n_shadow,
+                                                          n_nodes, n_prims, stk, bs, lbs, ox, oy);
         // Pixel sum of this round: pairwise butterfly over the pixel's g
         // lanes (missing samples are 0) = oracle.c:tree_sum; rounds are then
         // added in order in the leader's LDS slot.
@@ -444,7 +459,7 @@ __device__ __forceinline__ HitShade hit_shade(float d0, float d1, float d2, floa
 //     samples of all rounds together, in quadrant order), each recomputing
 //     its hit point from {t, sphere} with the same operations;
 //  4. per round in sample order: colours, pairwise sums, rounds in order.
-template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kOcc = false>
+template <bool kTiles, int kChunk, bool kStats, bool kProg, bool kOcc = false, bool kBin = false>
 __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl, void* stk,
                                                    uint32_t x, uint32_t y, uint32_t obase,
                                                    uint32_t& n_primary, uint32_t& n_shadow,
@@ -505,7 +520,17 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         float t = 0.0f;
         uint32_t idx = 0;
         bool hit = false;
-        if (valid) {
+        bool binned = false;
+        if (kBin) {  // (x, y) is the wave's one pixel: a 1x1 tile of its bin
+            uint2 bh;
+            binned = !bin_header(x, y, bh);
+            if (binned) {
+                KernArgs* kc = kernargs();
+                hit = bin_nearest(bh, x, y, 1u, 1u, valid, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2], d0, d1,
+                                  d2, t, idx);
+            }
+        }
+        if (valid && !binned) {
             RT_BS(kBsPhase);
             KernArgs* kc = kernargs();
             hit = walk<false, kChunk, true, kStats, true, false, true>(S, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2],
@@ -656,9 +681,10 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
 // and 72: the extra spills cost more; profiles/r02/sgpr_ab.log).
 // scene_kernel_w8 below is that build of the timed default.
 template <bool kTiles, int kChunk, bool kStats = true, bool kProg = false, bool kWaveQ = false,
-          bool kSort = false, bool kOcc = false>
+          bool kSort = false, bool kOcc = false, bool kBin = false>
 __device__ __forceinline__ void scene_body(FrameArgs a) {
     static_assert(!kOcc || !kStats, "stats frames walk: their counters are the oracle's");
+    static_assert(!kBin || (!kStats && kWaveQ), "bins: plain frames of the wave queue");
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
     float4* acc = lds;  // [256] running pixel sums (leader lanes' slots)
     const uint32_t wave = threadIdx.x >> 6;
@@ -853,10 +879,10 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
                 const unsigned long long tu0 = wall_clock64();
 #endif
                 if (kSort)
-                    shade_pixel_sorted<kTiles, kChunk, kStats, kProg, kOcc>(
+                    shade_pixel_sorted<kTiles, kChunk, kStats, kProg, kOcc, kBin>(
                         a, wl, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs);
                 else
-                    shade_wave_tile<kTiles, kChunk, kStats, kProg, !kSort, kOcc>(
+                    shade_wave_tile<kTiles, kChunk, kStats, kProg, !kSort, kOcc, kBin>(
                         a, acc, stk, ox, oy, obase, n_primary, n_shadow, n_nodes, n_prims, bs, lbs);
 #ifdef RT_TIMELINE
                 // per unit {start, end, hw_id << 32 | xcc << 16 | wave index}
@@ -959,10 +985,11 @@ __global__ void __launch_bounds__(kBlockThreads, kMinW) scene_kernel(FrameArgs a
 // The timed default for spp >= 8 (variant 13, plain frames): 8 waves per SIMD,
 // SGPRs capped so that they fit (see above).
 // kOcc: shadow rays answered from the occluder lists (a scene that has them)
-template <bool kTiles, bool kProg = false, bool kSort = false, bool kOcc = false>
+// kBin: primary rays answered from the frame's screen-space bins (a frame that built them)
+template <bool kTiles, bool kProg = false, bool kSort = false, bool kOcc = false, bool kBin = false>
 __global__ void __launch_bounds__(kBlockThreads, 8) __attribute__((amdgpu_num_sgpr(80)))
     scene_kernel_w8(FrameArgs a) {
-    scene_body<kTiles, 2, false, kProg, true, kSort, kOcc>(a);
+    scene_body<kTiles, 2, false, kProg, true, kSort, kOcc, kBin>(a);
 }
 
 // Camera-relative screen records of every leaf reference (and the kPrimPad
@@ -1313,7 +1340,7 @@ static bool sorted_rounds(const FrameArgs& a, bool on) {
 
 // kOcc: the plain (counter-free) instances answer shadow rays from the
 // scene's occluder lists; stats frames walk either way
-template <bool kTiles, bool kOcc>
+template <bool kTiles, bool kOcc, bool kBin>
 static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t lds, hipStream_t st) {
     if (sorted_rounds(a, sort)) {
         const size_t sl = sort_lds_bytes(a);
@@ -1321,11 +1348,11 @@ static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t 
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, true, true, true>, a, sl, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, true, true, kOcc>, a, sl, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, true, true, kOcc, kBin>, a, sl, st, 8);
         } else if (a.count_work) {
             launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true, true>, a, sl, st);
         } else {
-            launch_waveq(scene_kernel_w8<kTiles, false, true, kOcc>, a, sl, st, 8);
+            launch_waveq(scene_kernel_w8<kTiles, false, true, kOcc, kBin>, a, sl, st, 8);
         }
         return;
     }
@@ -1334,7 +1361,7 @@ static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t 
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, true, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, true, false, kOcc>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, true, false, kOcc, kBin>, a, lds, st, 8);
         } else if (a.count_work) {
             launch_persistent(scene_kernel<kTiles, 1, 2, true, true>, a, n_bt, lds, st);
         } else {
@@ -1363,7 +1390,7 @@ static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t 
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc, kBin>, a, lds, st, 8);
             break;
         case kVariantWaveQ:  // the spp >= 8 default: per-wave scheduling over per-XCD queues.
             // Timed (plain) frames: 8 waves/SIMD with SGPRs capped at 80
@@ -1372,7 +1399,7 @@ static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t 
             if (a.count_work)
                 launch_waveq(scene_kernel<kTiles, 7, 2, true, false, true>, a, lds, st);
             else
-                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc>, a, lds, st, 8);
+                launch_waveq(scene_kernel_w8<kTiles, false, false, kOcc, kBin>, a, lds, st, 8);
             break;
         default:  // rejected by variant_available() before any launch
             break;
@@ -1385,10 +1412,30 @@ static void launch_scene_o(const FrameArgs& a, bool sort, uint32_t n_bt, size_t 
 // removed in round 3; their A/B logs stay under profiles/.
 template <bool kTiles>
 static void launch_scene_t(const FrameArgs& a, bool sort, uint32_t n_bt, size_t lds, hipStream_t st) {
-    if (a.sc.prim_occ && a.sc.occ_sp && a.shadows && !a.count_work)
-        launch_scene_o<kTiles, true>(a, sort, n_bt, lds, st);
+    // (bins: set only for a frame whose instance reads them, frame_reads_bins)
+    const bool bin = a.bin_hdr && a.bin_ent && a.bin_info && !a.count_work;
+    const bool occ = a.sc.prim_occ && a.sc.occ_sp && a.shadows && !a.count_work;
+    if (occ && bin)
+        launch_scene_o<kTiles, true, true>(a, sort, n_bt, lds, st);
+    else if (occ)
+        launch_scene_o<kTiles, true, false>(a, sort, n_bt, lds, st);
+    else if (bin)
+        launch_scene_o<kTiles, false, true>(a, sort, n_bt, lds, st);
     else
-        launch_scene_o<kTiles, false>(a, sort, n_bt, lds, st);
+        launch_scene_o<kTiles, false, false>(a, sort, n_bt, lds, st);
+}
+
+// Whether launch_scene runs this plain frame on a scene_kernel_w8 instance
+// (the ones that read bins): launch_scene_o's choices, restated.
+bool frame_reads_bins(const FrameArgs& a_in, bool sort) {
+    FrameArgs a = a_in;
+    if (a.count_work) return false;
+    if (a.accum) a.variant = kVariantLaneUnified;
+    wave_tile_shape(a.spp, a.spw, a.g, a.ppw, a.tw, a.th);
+    a.rounds = (a.spp + a.spw - 1) / a.spw;
+    if (sorted_rounds(a, sort)) return true;
+    if (a.accum) return a.spp >= 8u;
+    return a.variant == kVariantWaveQ || a.variant == kVariantWaveQLow;
 }
 
 bool variant_available(uint32_t v) {

@@ -259,6 +259,32 @@ static_assert(kOccCamK * kOccCamGate <= kOccNormM && kOccCamK * kOccCamGate <= k
                   kOccCamK * kOccCamGate + 6.0 <= kOccSelfM,
               "the list bounds cover every camera inside the gate");
 
+// One entry of a screen-space bin's list (32 bytes, read by scalar loads):
+// the sphere's record as the walk's exact test reads it (prim_sp[ref]), its
+// index (the t-tie rule), one leaf reference of it (shading by reference),
+// the pixels of its rectangle inside this bin (x0 | x1 << 4 | y0 << 8 |
+// y1 << 12, bin-local) and the near bound (a lower bound on any accepted t).
+struct BinEntry {
+    float cx, cy, cz, r;
+    uint32_t idx, ref, rect;
+    float near_t;
+};
+static_assert(sizeof(BinEntry) == 32, "two uint4 per entry");
+// bin_info words (device, mirrored to the renderer's pinned copy)
+enum BinInfoWord : uint32_t {
+    kBinInfoFlag = 0,   // 0: binned; kBinFlag* bits: the frame walks
+    kBinInfoWide,       // spheres in the wide list
+    kBinInfoEntries,    // total entries the frame's bins need
+    kBinInfoNonEmpty,   // bins with at least one entry
+    kBinInfoLongest,    // the longest list
+    kBinInfoOver,       // bins over the cap (their pixels walk)
+    kBinInfoFrame,      // the frame id the words belong to
+    kBinInfoWords = 8
+};
+constexpr uint32_t kBinFlagCapacity = 1u;  // the entries do not fit the buffer
+constexpr uint32_t kBinFlagWide = 2u;      // the wide list overflowed
+constexpr uint32_t kBinFlagDense = 4u;     // mean list length over kBinMeanMax
+
 // Spheres per wave in the LDS leaf buffer (a leaf of >= kLeafBuf uses global loads)
 constexpr uint32_t kLeafBuf = 32;
 
@@ -328,6 +354,17 @@ struct FrameArgs {
     uint32_t* qerr;
     uint32_t frame_id;         // nonzero, per renderer
     uint32_t test_fault_queue; // test only (RT_TEST_FAULT=queue:k): the frame reports itself failed
+    // Screen-space bins of this frame (screen_bins.hip, DESIGN.md 5.1 round 10;
+    // all null: the frame's primary rays walk).  bin_hdr[by * bin_nbx + bx] =
+    // {first entry, count | kBinWalk} of the 8x8-pixel bin, bin_ent the
+    // entries (BinEntry, two uint4 each), bin_wide the frame-level list every
+    // pixel tests, bin_info[0] the frame's fallback flag (non-zero: every wave
+    // walks) and bin_info[1] the wide list's length.
+    const uint2* bin_hdr;
+    const uint4* bin_ent;
+    const uint4* bin_wide;
+    const uint32_t* bin_info;
+    uint32_t bin_nbx;
 #ifdef RT_TIMELINE
     unsigned long long* timeline;  // diagnostic build: 4 words per wave
 #endif

@@ -109,6 +109,7 @@ class KernelRenderer:
                  variant: int = 0, opt_off: int = 0, host_build: bool = False,
                  progressive: bool = False, cell_table: Optional[int] = None,
                  compat_fma: bool = False, pad_fill: int = 0, occluders: bool = True,
+                 bins: bool = True,
                  devices: Optional[Sequence[int]] = None, transport: str = "auto"):
         """devices: render every frame across these HIP devices of this process
         (rt_create_multi: tiles round-robin, slabs gathered to devices[0] over
@@ -139,6 +140,8 @@ class KernelRenderer:
             flags |= _lib.RT_FLAG_COMPAT_FMA
         if not occluders:  # A/B: every shadow ray walks the octree
             flags |= _lib.RT_FLAG_NO_OCCLUDERS
+        if not bins:  # A/B: every primary ray walks the octree
+            flags |= _lib.RT_FLAG_NO_BINS
         # pad_fill (test-only): 0 zeros, 1 NaN, 2 covering spheres after the last leaf list
         if not 0 <= int(pad_fill) <= 2:
             raise ValueError("pad_fill must be 0, 1 or 2")
@@ -289,6 +292,23 @@ class KernelRenderer:
         check(self._lib.rt_export_occluders(self._h, _vptr(off), _vptr(cnt), _vptr(idx), _vptr(refs)),
               self._h)
         return off[:n], cnt[:n], idx[:e], refs[:m]
+
+    def bin_info(self) -> dict:
+        """rt_get_bin_info: the last frame's screen-space bins (waits for it)."""
+        info = _lib.RtBinInfo()
+        check(self._lib.rt_get_bin_info(self._h, ctypes.byref(info)), self._h)
+        return info.as_dict()
+
+    def export_bins(self):
+        """The last frame's bins as host arrays (rt_export_bins): (bins, 2)
+        headers {first entry, count | 0xFFFFFFFF}, the lists' sphere indices,
+        and the wide list's sphere indices."""
+        bi = self.bin_info()
+        hdr = np.zeros((max(bi["bins"], 1), 2), np.uint32)
+        idx = np.zeros(max(bi["entries"], 1), np.uint32)
+        wide = np.zeros(max(bi["wide"], 1), np.uint32)
+        check(self._lib.rt_export_bins(self._h, _vptr(hdr), _vptr(idx), _vptr(wide)), self._h)
+        return hdr[:bi["bins"]], idx[:bi["entries"]], wide[:bi["wide"]]
 
     def scene_info(self) -> dict:
         info = RtSceneInfo()
