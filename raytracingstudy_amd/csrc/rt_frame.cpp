@@ -353,7 +353,8 @@ int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     if (r->bin_skip_gen != r->scene_gen) r->bin_dense_skip = 0, r->bin_skip_gen = r->scene_gen;
     if (!r->bin_dense_skip && r->bin_last_frame && r->bin_mirror[kBinInfoFrame] == r->bin_last_frame &&
         r->bin_mirror[kBinInfoFlag] == kBinFlagDense) {
-        r->bin_dense_skip = kBinDenseSkip + 1u;
+        // (this frame is the first of the kBinDenseSkip skipped ones: the block below counts it)
+        r->bin_dense_skip = kBinDenseSkip;
         r->bin_last_frame = 0;  // (this observation is used up: the probe makes the next one)
     }
     if (r->bin_dense_skip) {

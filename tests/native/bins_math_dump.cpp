@@ -3,6 +3,8 @@
 //   rect  W H shrink(f64) K[9] R[9] o[3] file  -> per sphere of `file` (raw f32
 //         {cx, cy, cz, r} records): class x0 y0 x1 y1 near(f32 bits)
 //   camok K[9] R[9] o[3]                       -> 0 | 1
+//   framegate W H K[9] R[9] o[3]               -> 0 | 1: the host's gate of a W x H
+//         frame (rt_frame.cpp screen_bins: bins_camera_ok and cam8_basis)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +12,7 @@
 #include <vector>
 
 #include "../../raytracingstudy_amd/csrc/rt_bins_math.h"
+#include "../../raytracingstudy_amd/csrc/rt_frame_math.h"
 
 namespace {
 int g_argc;
@@ -72,6 +75,13 @@ int main(int argc, char** argv) {
         vec(R, 9);
         vec(o, 3);
         printf("%d\n", rtamd::bins_camera_ok(K, R, o) ? 1 : 0);
+    } else if (cmd == "framegate") {
+        const uint32_t W = u32(), H = u32();
+        float B[9];
+        vec(K, 9);
+        vec(R, 9);
+        vec(o, 3);
+        printf("%d\n", rtamd::bins_camera_ok(K, R, o) && rtamd::cam8_basis(K, R, W, H, B) ? 1 : 0);
     } else {
         fprintf(stderr, "bins_math_dump: unknown command '%s'\n", cmd.c_str());
         return 2;

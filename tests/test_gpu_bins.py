@@ -270,6 +270,58 @@ def test_dense_frame_walks(gpu, oracle_scenes, hooks):
         _check_frames(r, oracle_scenes["U"], 32, 24, 8)
 
 
+def test_dense_skip_cadence(gpu, oracle_scenes, hooks):
+    """After a probe the device rule found dense, the next kBinDenseSkip = 15
+    plain frames build no bins, then one probes again: "once in 16 frames"
+    (csrc/rt_bins_math.h).  bin_info() after every frame synchronises, so each
+    observation is deterministic.  A stats frame in between does not count, a
+    pose change in the middle of the skip renders the new pose, and set_scene
+    starts over; every frame's bytes are the oracle's."""
+    hooks(mean=None)
+    w, h, spp, skip = 32, 24, 8, 15
+    moved = look_at_pose((0.1, 0.9, 2.0))
+    with _renderer(SCENES["U"], w, h, spp) as r:
+        _, K = r.camera()
+        refs = {k: oracle_scenes["U"].render(w, h, p, K, spp=spp) for k, p in
+                (("scene", scene_pose()), ("moved", moved))}
+
+        def frame(pose="scene", stats=False):
+            st = r.render(stats=stats)
+            bi = r.bin_info()
+            ref8, ref32, cnt = refs[pose]
+            assert np.array_equal(r.readback(), ref8) and np.array_equal(r.readback_radiance(), ref32)
+            if stats:
+                assert (st.primary_rays, st.shadow_rays) == (int(cnt[0]), int(cnt[1]))
+            return bi
+
+        def probe(pose="scene"):
+            bi = frame(pose)
+            assert bi["enabled"] == 0 and bi["reason"] == "dense", bi
+            assert bi["bins"] == 4 * 3 and bi["entries"] > 48 * bi["non_empty_bins"] > 0, bi
+
+        def skipped(pose="scene"):
+            bi = frame(pose)
+            assert bi["enabled"] == 0 and bi["reason"] == "dense", bi
+            assert bi["bins"] == 0 and bi["entries"] == 0, bi
+
+        probe()
+        for k in range(skip):
+            if k == 4:      # a stats frame walks and does not advance the count
+                assert frame(stats=True)["reason"] == "kernel"
+            if k == 7:
+                r.setPosition(moved)
+            skipped("moved" if k >= 7 else "scene")
+        probe("moved")
+        skipped("moved")
+        skipped("moved")
+        r.setPosition(scene_pose())
+        r.set_scene(*SCENES["U"])     # a new scene generation: the count starts over
+        probe()
+        for k in range(skip):
+            skipped()
+        probe()
+
+
 # ---- 4. a moving camera ------------------------------------------------------
 
 def test_moving_camera(gpu, hooks, oracle_scenes):
