@@ -36,6 +36,8 @@
  *     include/octree.h:19-21; no ray entry point)
  *   (none: Octree::traverse is a stub; the Displayer's    rt_pick
  *     mouse input selects nothing)
+ *   (none: as above; one hit was the most a ray           rt_trace_rays_multi / rt_pick_multi
+ *     could report)
  *   (none: one colour per pixel,                          rt_render_gbuffer
  *     src/renderer.cu:57-82)
  *   (none: no error reporting, all void)                  rt_last_error
@@ -418,6 +420,33 @@ int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kin
  * for the answer.  hit_out as above; point_out (may be NULL) = origin + t * dir.
  * The Displayer's mouse position goes here. */
 int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]);
+
+/* Ordered multi-hit queries: the k nearest spheres along each ray (click-through
+ * picking, several lidar returns per beam, an integrator's ordered surface
+ * list).  For one ray the accepted set is every scene sphere whose t (the
+ * intersection test above: the near root, or the far root when the near one is
+ * not past tmin) lies in tmin < t < tmax; each sphere counts once.  The answer
+ * is the k smallest of the set by (t ascending, then sphere index ascending):
+ * RT_QUERY_NEAREST's tie rule extended, and for k = 1 its answer exactly.
+ *   dev_hits    n*k rt_hit, ray-major: ray i's hits at [i*k, i*k + k) in that
+ *               order; slots past the ray's count hold {the ray's tmax,
+ *               RT_NO_HIT}.  Every slot of every ray is written.
+ *   dev_counts  n uint32 or NULL: min(k, size of the accepted set).
+ * stream, ordering and stats as rt_trace_rays: primary_rays = n, nodes_visited
+ * / prims_tested the walk's own counts summed over the rays (for k = 1 the
+ * nearest query's; the walk runs with k rounded up to 1, 2, 4, 8 or 16).
+ * k == 0 or k > RT_MULTIHIT_MAX: RT_E_INVALID.  n == 0: RT_OK, nothing
+ * launched.  A NULL dev_rays / dev_hits with n > 0: RT_E_INVALID.  No scene:
+ * RT_E_NOSCENE.  Rays with a NaN or infinite component have an empty set.
+ * Reads scene state only; a multi-device handle answers from devices[0]. */
+#define RT_MULTIHIT_MAX 16
+int rt_trace_rays_multi(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t k,
+                        void* dev_hits, void* dev_counts, void* stream, rt_stats* stats);
+/* rt_pick's ray (Camera::getRay, tmin = 0, tmax = +inf) as a 1-ray multi-hit
+ * query; waits for the answer.  hits_out has room for k rt_hit, filled as
+ * dev_hits above; count_out (may be NULL) as dev_counts.  The Displayer's
+ * repeated click on one spot walks down this list. */
+int rt_pick_multi(rt_renderer* r, float u, float v, uint32_t k, rt_hit* hits_out, uint32_t* count_out);
 
 /* ---- first-hit G-buffer --------------------------------------------------- */
 /* The per-pixel geometry of the frame the current size and camera would

@@ -160,6 +160,22 @@ public:
         if (hit) *hit = h;
         return h.sphere != RT_NO_HIT;
     }
+    // the k nearest spheres along each ray, by (t, sphere index)
+    // (rt_trace_rays_multi): n rt_ray -> n*k rt_hit, ray-major, and n uint32
+    // counts (or null), all in device memory; 1 <= k <= RT_MULTIHIT_MAX
+    void traceRaysMulti(const void* dev_rays, uint32_t n, uint32_t k, void* dev_hits,
+                        void* dev_counts = nullptr, void* stream = nullptr,
+                        rt_stats* stats = nullptr) {
+        check(rt_trace_rays_multi(r_, dev_rays, n, k, dev_hits, dev_counts, stream, stats), r_);
+    }
+    // the k nearest spheres under image coordinates (u, v), front to back
+    // (rt_pick_multi): a repeated click selects hits[1], hits[2], ...; returns
+    // how many of hits[0 .. k) are spheres
+    uint32_t pickMulti(float u, float v, uint32_t k, rt_hit* hits) {
+        uint32_t count = 0;
+        check(rt_pick_multi(r_, u, v, k, hits, &count), r_);
+        return count;
+    }
     // first-hit G-buffer of the current camera (rt_render_gbuffer): W*H rt_hit,
     // float[4] normals and packed RGBA8 albedo in device memory, each optional
     void renderGBuffer(void* dev_hits, void* dev_normals = nullptr, void* dev_albedo = nullptr,

@@ -55,6 +55,7 @@ RT_MAX_DEVICES = 16
 RT_NO_HIT = 0xFFFFFFFF    # rt_hit.sphere of a miss
 RT_QUERY_NEAREST = 0
 RT_QUERY_ANY = 1
+RT_MULTIHIT_MAX = 16      # rt_trace_rays_multi / rt_pick_multi: the largest k
 
 _f3 = ctypes.c_float * 3
 
@@ -244,6 +245,9 @@ SIGNATURES = {
     "rt_unpack_tiles": (_int, [_P, _P, _P, _u32, _u32, _P, _P]),
     "rt_trace_rays": (_int, [_P, _P, _u32, _u32, _P, _P, ctypes.POINTER(RtStats)]),
     "rt_pick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
+    "rt_trace_rays_multi": (_int, [_P, _P, _u32, _u32, _P, _P, _P, ctypes.POINTER(RtStats)]),
+    "rt_pick_multi": (_int, [_P, ctypes.c_float, ctypes.c_float, _u32, ctypes.POINTER(RtHit),
+                             ctypes.POINTER(_u32)]),
     "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),

@@ -277,6 +277,8 @@ int rt_destroy(rt_renderer* r) {
     r->q_counters.release();
     r->q_ray.release();
     r->q_hit.release();
+    r->q_multi_hits.release();
+    r->q_multi_count.release();
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();

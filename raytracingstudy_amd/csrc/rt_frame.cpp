@@ -652,6 +652,26 @@ int query_stats_read(rt_renderer* r, const unsigned long long* ctr, rt_stats* st
     return RT_OK;
 }
 
+// rt_pick's ray through image coordinates (u, v): tmin = 0, tmax = +inf.
+void pick_ray(const rt_renderer* r, float u, float v, float4 ray[2]) {
+    // Camera::getRay (include/camera.h:24-41) in source order on the host (built
+    // with -ffp-contract=off, IEEE division and sqrt): the same bits as the CPU oracle's getRay
+    const float* K = r->K;
+    const float* P = r->pose;
+    const float dx = (u - K[2]) / K[0];
+    const float dy = (v - K[5]) / K[4];
+    const float dz = 1.0f;
+    float wx = P[0] * dx + P[4] * dy + P[8] * dz;
+    float wy = P[1] * dx + P[5] * dy + P[9] * dz;
+    float wz = P[2] * dx + P[6] * dy + P[10] * dz;
+    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
+    wx /= len;
+    wy /= len;
+    wz /= len;
+    ray[0] = make_float4(P[12], P[13], P[14], 0.0f);
+    ray[1] = make_float4(wx, wy, wz, INFINITY);
+}
+
 }  // namespace
 
 extern "C" {
@@ -758,21 +778,8 @@ int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kin
 int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]) {
     if (!r || !hit_out) return fail(r, RT_E_INVALID, "rt_pick: null argument");
     if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick: no scene (rt_set_scene first)");
-    // Camera::getRay (include/camera.h:24-41) in source order on the host (built
-    // with -ffp-contract=off, IEEE division and sqrt): the same bits as the CPU oracle's getRay
-    const float* K = r->K;
-    const float* P = r->pose;
-    const float dx = (u - K[2]) / K[0];
-    const float dy = (v - K[5]) / K[4];
-    const float dz = 1.0f;
-    float wx = P[0] * dx + P[4] * dy + P[8] * dz;
-    float wy = P[1] * dx + P[5] * dy + P[9] * dz;
-    float wz = P[2] * dx + P[6] * dy + P[10] * dz;
-    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
-    wx /= len;
-    wy /= len;
-    wz /= len;
-    const float4 ray[2] = {make_float4(P[12], P[13], P[14], 0.0f), make_float4(wx, wy, wz, INFINITY)};
+    float4 ray[2];
+    pick_ray(r, u, v, ray);
     int st;
     if ((st = set_device(r))) return st;
     if ((st = ensure(r, r->q_ray, 2)) || (st = ensure(r, r->q_hit, 1))) return st;
@@ -786,9 +793,75 @@ int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3
     memcpy(&hit_out->t, &h.x, sizeof(float));
     hit_out->sphere = h.y;
     if (point_out) {
-        const float o[3] = {P[12], P[13], P[14]}, d[3] = {wx, wy, wz};
+        const float o[3] = {ray[0].x, ray[0].y, ray[0].z}, d[3] = {ray[1].x, ray[1].y, ray[1].z};
         for (int i = 0; i < 3; ++i) point_out[i] = o[i] + hit_out->t * d[i];
     }
+    return RT_OK;
+}
+
+// Ordered multi-hit queries: the k nearest spheres of each ray
+// by (t, sphere index).  A query like rt_trace_rays: scene state only, the
+// query path's own stat lines, the same stream ordering.
+int rt_trace_rays_multi(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t k, void* dev_hits,
+                        void* dev_counts, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_trace_rays_multi: null handle");
+    if (k == 0 || k > RT_MULTIHIT_MAX)
+        return fail(r, RT_E_INVALID, "rt_trace_rays_multi: k must be 1 .. RT_MULTIHIT_MAX");
+    if (!r->has_scene)
+        return fail(r, RT_E_NOSCENE, "rt_trace_rays_multi: no scene (rt_set_scene first)");
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    if (!dev_rays || !dev_hits) return fail(r, RT_E_INVALID, "rt_trace_rays_multi: null buffer");
+    int st;
+    if ((st = set_device(r))) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    // the kernel's leading argument is a FrameArgs (rt_multihit.hip): the scene, the rest zero
+    FrameArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sc = r->sc;
+    unsigned long long* ctr = nullptr;
+    if (stats && (st = query_stats_begin(r, hs, ctr))) return st;
+    hipError_t e = launch_multihit(a, dev_rays, dev_hits, dev_counts, n, k, ctr, hs);
+    if (e != hipSuccess) return hip_fail(r, e, "rt_trace_rays_multi: kernel launch");
+    if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
+    if ((st = mark_queued(r, hs))) return st;
+    if (stats) {
+        if ((st = query_stats_read(r, ctr, stats))) return st;
+        stats->primary_rays = n;
+    }
+    return RT_OK;
+}
+
+int rt_pick_multi(rt_renderer* r, float u, float v, uint32_t k, rt_hit* hits_out, uint32_t* count_out) {
+    if (!r || !hits_out) return fail(r, RT_E_INVALID, "rt_pick_multi: null argument");
+    if (k == 0 || k > RT_MULTIHIT_MAX)
+        return fail(r, RT_E_INVALID, "rt_pick_multi: k must be 1 .. RT_MULTIHIT_MAX");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick_multi: no scene (rt_set_scene first)");
+    float4 ray[2];
+    pick_ray(r, u, v, ray);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q_ray, 2)) || (st = ensure(r, r->q_multi_hits, RT_MULTIHIT_MAX)) ||
+        (st = ensure(r, r->q_multi_count, 1)))
+        return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q_ray.p, ray, sizeof(ray), hipMemcpyHostToDevice, hs));
+    if ((st = rt_trace_rays_multi(r, r->q_ray.p, 1, k, r->q_multi_hits.p, r->q_multi_count.p, hs, nullptr)))
+        return st;
+    uint2 h[RT_MULTIHIT_MAX];
+    uint32_t count = 0;
+    RT_HIP(r, hipMemcpyAsync(h, r->q_multi_hits.p, k * sizeof(uint2), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipMemcpyAsync(&count, r->q_multi_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    for (uint32_t s = 0; s < k; ++s) {
+        memcpy(&hits_out[s].t, &h[s].x, sizeof(float));
+        hits_out[s].sphere = h[s].y;
+    }
+    if (count_out) *count_out = count;
     return RT_OK;
 }
 

@@ -44,6 +44,10 @@ hipError_t launch_cam8_screen(const float4* prim_sp, uint32_t n, const float o[3
 // rt_query.hip: n rays (rt_ray) -> n hits (rt_hit) against a.sc; counters != null: a stats launch
 hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32_t n, bool any,
                         unsigned long long* counters, hipStream_t st);
+// rt_multihit.hip: n rays -> n x k hits (ray-major, the k nearest by (t, sphere index)) and n
+// counts (may be null) against a.sc; 1 <= k <= RT_MULTIHIT_MAX; counters != null: a stats launch
+hipError_t launch_multihit(const FrameArgs& a, const void* rays, void* hits, void* counts, uint32_t n,
+                           uint32_t k, unsigned long long* counters, hipStream_t st);
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
@@ -331,6 +335,9 @@ struct RendererState {
     DevBuf<unsigned long long> q_counters;
     DevBuf<float4> q_ray;
     DevBuf<uint2> q_hit;
+    // rt_pick_multi's hits (up to RT_MULTIHIT_MAX) and its count
+    DevBuf<uint2> q_multi_hits;
+    DevBuf<uint32_t> q_multi_count;
     rt_scene_info info{};
     std::string err;
     // multi-device handle (rt_create_multi): this renderer is devices[0]'s

@@ -1,0 +1,112 @@
+// rt_multihit.hip — ordered multi-hit ray queries (rt_trace_rays_multi,
+// rt_pick_multi; include/rt.h): the k nearest spheres along each
+// ray, by (t, then the caller's sphere index).  The reference has no
+// counterpart (Octree::traverse is a stub, include/octree.h:19-21).
+//
+// One caller-supplied ray per lane through walk<> (rt_walk.h) in its generic
+// mode with a MultiHits<K> buffer: the frames' plane(), isect and step rules,
+// the nearest rule's bound taken from the buffer's last entry.  Compiled like
+// rt_query.hip (-ffp-contract=off, IEEE division / sqrt).
+#include <hip/hip_runtime.h>
+
+#include "rt_params.h"
+#include "rt_walk.h"
+
+namespace rtamd {
+
+struct MultiQueryArgs {
+    const float4* rays;            // n x {origin.xyz, tmin}, {dir.xyz, tmax}
+    uint2* hits;                   // n x k x {t bits, sphere index | kNoHit}, ray-major
+    uint32_t* counts;              // n, or null
+    uint32_t n;
+    uint32_t k;                    // the caller's k: 1 <= k <= K
+    unsigned long long* counters;  // stats launches: 8 lines of kStatLineStride words
+};
+
+__device__ __forceinline__ unsigned long long multi_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// One ray per lane, 256-thread blocks, the K-entry buffer in registers (K is
+// the caller's k rounded up to a compiled size: the walk keeps the K nearest
+// and the lane writes the first k of them, so slots, fillers and counts are
+// exact for k).  A ray is two coalesced dwordx4 loads, its hits k dwordx2
+// stores.  FrameArgs leads the argument block for rt_query.hip's reason:
+// kernargs() reinterprets the argument segment as FrameArgs.  The dynamic LDS
+// is the per-lane ancestor stack alone, [level][thread].
+template <int K, bool kStats>
+__global__ void __launch_bounds__(kBlockThreads) multihit_kernel(FrameArgs a, MultiQueryArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    uint2* stk = reinterpret_cast<uint2*>(lds) + threadIdx.x;
+    const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
+    uint32_t n_nodes = 0, n_prims = 0;
+    if (i < q.n) {
+        const float4 r0 = q.rays[2u * static_cast<size_t>(i)];
+        const float4 r1 = q.rays[2u * static_cast<size_t>(i) + 1u];
+        MultiHits<K> mh;
+        mh.clear(r1.w);  // a free slot reports the ray's tmax
+        float t_unused = 0.0f;
+        uint32_t ref_unused = kNoHit;
+        walk<false, 2, false, kStats, false, false, false, true, K>(
+            a.sc, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r0.w, r1.w, t_unused, ref_unused, n_nodes,
+            n_prims, stk, false, nullptr, ~0u, &mh);
+        uint2* out = q.hits + static_cast<size_t>(i) * q.k;
+        uint32_t count = 0;
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            if (static_cast<uint32_t>(s) < q.k) {
+                const bool hit = mh.ref[s] != kNoHit;
+                // the caller's sphere index, not the leaf reference
+                const uint32_t sphere = hit ? a.sc.prim_idx[mh.ref[s]] : kNoHit;
+                out[s] = make_uint2(__float_as_uint(mh.t[s]), sphere);
+                count += hit ? 1u : 0u;
+            }
+        }
+        if (q.counts) q.counts[i] = count;
+    }
+    if (kStats) {
+        // rt_query.hip's layout: words 2 and 3 of one line per XCD group
+        const unsigned long long s2 = multi_wave_sum(n_nodes);
+        const unsigned long long s3 = multi_wave_sum(n_prims);
+        if ((threadIdx.x & 63u) == 0) {
+            unsigned long long* c = q.counters + (blockIdx.x & 7u) * kStatLineStride;
+            atomicAdd(c + 2, s2);
+            atomicAdd(c + 3, s3);
+        }
+    }
+}
+
+template <int K>
+static void launch_k(const FrameArgs& a, const MultiQueryArgs& q, dim3 grid, size_t lds, hipStream_t st) {
+    if (q.counters) hipLaunchKernelGGL((multihit_kernel<K, true>), grid, dim3(kBlockThreads), lds, st, a, q);
+    else hipLaunchKernelGGL((multihit_kernel<K, false>), grid, dim3(kBlockThreads), lds, st, a, q);
+}
+
+// a.sc is the scene; the rest of `a` is unused by the kernel (see above).
+// 1 <= k <= 16 (the caller checked); counts may be null; counters != null: a
+// stats launch (the caller zeroed its 8 lines).
+hipError_t launch_multihit(const FrameArgs& a, const void* rays, void* hits, void* counts, uint32_t n,
+                           uint32_t k, unsigned long long* counters, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (k == 0 || k > 16u) return hipErrorInvalidValue;
+    MultiQueryArgs q;
+    q.rays = static_cast<const float4*>(rays);
+    q.hits = static_cast<uint2*>(hits);
+    q.counts = static_cast<uint32_t*>(counts);
+    q.n = n;
+    q.k = k;
+    q.counters = counters;
+    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlockThreads - 1u) / kBlockThreads));
+    const size_t lds = static_cast<size_t>(stack_levels(a.sc)) * kBlockThreads * sizeof(uint2);
+    // compiled sizes 1, 2, 4, 8, 16: k = 1 runs the nearest walk's own stop rule
+    if (k == 1) launch_k<1>(a, q, grid, lds, st);
+    else if (k == 2) launch_k<2>(a, q, grid, lds, st);
+    else if (k <= 4) launch_k<4>(a, q, grid, lds, st);
+    else if (k <= 8) launch_k<8>(a, q, grid, lds, st);
+    else launch_k<16>(a, q, grid, lds, st);
+    return hipGetLastError();
+}
+
+}  // namespace rtamd

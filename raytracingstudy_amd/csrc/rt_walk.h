@@ -1,5 +1,6 @@
 // rt_walk.h — the per-lane octree walk and its helpers, shared by the frame
-// kernels (rt_kernels.hip) and the ray-query kernel (rt_query.hip).  Device
+// kernels (rt_kernels.hip) and the ray-query kernels (rt_query.hip,
+// rt_multihit.hip, rt_gbuffer.hip).  Device
 // code only; included inside a HIP translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -155,6 +156,62 @@ __device__ __forceinline__ uint32_t leaf_buf_base(const SceneArgs& S, bool sorte
     return head + wave * kLeafBuf;
 }
 
+// One lane's K nearest hits of a multi-hit walk (rt_multihit.hip, DESIGN.md
+// 5.9): {t, leaf reference}, sorted by (t, then the caller's sphere index), a
+// free slot {the ray's tmax, kNoHit} (isect accepts t < tmax only, so a free
+// slot sorts after every hit and t[K - 1] is the walk's bound either way).
+// Every index below is a compile-time constant once the loops are unrolled:
+// the arrays are registers, never scratch.
+template <int K>
+struct MultiHits {
+    float t[K > 0 ? K : 1];
+    uint32_t ref[K > 0 ? K : 1];
+    __device__ __forceinline__ void clear(float tmax) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            t[i] = tmax;
+            ref[i] = kNoHit;
+        }
+    }
+    // An accepted sphere.  It enters iff it sorts before the K-th entry and is
+    // not held already.  A sphere met again in a later leaf has the same t
+    // bits, so the sphere indices are loaded only when an entry's t equals th
+    // exactly (the nearest walk's tie load); a sphere evicted earlier sorts
+    // after the K-th entry and is rejected by the same comparison.
+    __device__ __forceinline__ void offer(const uint32_t* __restrict__ prim_idx, float th, uint32_t r) {
+        if (!(th <= t[K - 1])) return;
+        uint32_t pos = 0;  // entries that sort before the candidate
+        bool tie = false;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            pos += t[i] < th ? 1u : 0u;
+            tie |= t[i] == th;
+        }
+        bool held = false;
+        if (tie) {
+            // (an entry whose t equals th is a hit, never a free slot: th <
+            // tmax, so ref[i] below is a leaf reference)
+            const uint32_t ci = prim_idx[r];
+#pragma unroll
+            for (int i = 0; i < K; ++i)
+                if (t[i] == th) {
+                    const uint32_t ei = prim_idx[ref[i]];
+                    held |= ei == ci;
+                    pos += ei < ci ? 1u : 0u;
+                }
+        }
+        if (held || pos >= static_cast<uint32_t>(K)) return;
+#pragma unroll
+        for (int i = K - 1; i >= 0; --i) {
+            const bool below = static_cast<uint32_t>(i) > pos;  // shifts down one slot
+            const bool here = static_cast<uint32_t>(i) == pos;
+            const int up = i > 0 ? i - 1 : 0;  // (slot 0 never shifts: pos >= 0)
+            t[i] = here ? th : below ? t[up] : t[i];
+            ref[i] = here ? r : below ? ref[up] : ref[i];
+        }
+    }
+};
+
 // Grid-space octree walk (DESIGN.md "Octree walk"): mirrored origin so every
 // direction component is >= 0 (the Revelles entry step of hit_sphere,
 // src/renderer.cu:23-43), cell planes at integer grid coordinates, descend by
@@ -181,15 +238,26 @@ __device__ __forceinline__ uint32_t leaf_buf_base(const SceneArgs& S, bool sorte
 // lb_u: the wave's LDS leaf buffer (scene_body's leaf_buf_base), read only by
 // a walk that stages leaves: a frame's nearest walk without kCam8.  The other
 // walks pass none.
+// kMulti > 0: a multi-hit walk (rt_multihit.hip), a generic
+// nearest walk that keeps the kMulti smallest (t, sphere index) in *mh (which
+// the caller cleared to the ray's tmax) instead of one best hit: every
+// accepted sphere is offered to mh, and mh's last t takes best_t's place in
+// the stop rule.  isect keeps the ray's own tmax, so a sphere tied with the
+// last entry at a lower index is still seen.  Returns whether mh holds a hit;
+// tout and iout are left alone.
 template <bool kAnyHitT, int kChunk = 2, bool kDynAny = false, bool kStats = true,
-          bool kNoStack = false, bool kShadowL = false, bool kCam8 = false, bool kGeneric = false>
+          bool kNoStack = false, bool kShadowL = false, bool kCam8 = false, bool kGeneric = false,
+          int kMulti = 0>
 __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, float o2, float d0,
                                      float d1, float d2, float tmin, float tmax, float& tout,
                                      uint32_t& iout, uint32_t& n_nodes, uint32_t& n_prims,
                                      uint2* __restrict__ stk, bool any_rt = false,
-                                     uint32_t* bs = nullptr, uint32_t lb_u = ~0u) {
+                                     uint32_t* bs = nullptr, uint32_t lb_u = ~0u,
+                                     MultiHits<kMulti>* mh = nullptr) {
     static_assert(!kShadowL || kAnyHitT || kDynAny, "a shadow walk along L is an any-hit walk");
     static_assert(!kGeneric || (!kShadowL && !kCam8), "a generic ray has no frame to screen against");
+    static_assert(kMulti == 0 || (kGeneric && !kAnyHitT && !kDynAny),
+                  "a multi-hit walk is a generic nearest walk");
     const bool kAnyHit = kDynAny ? any_rt : kAnyHitT;
     const uint32_t D = S.max_depth;
     const uint32_t G = 1u << D;
@@ -303,6 +371,10 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
                 tout = th;
                 if (kGeneric) iout = ref;
                 return true;
+            }
+            if constexpr (kMulti > 0) {
+                mh->offer(S.prim_idx, th, ref);
+                return false;
             }
             if (th < best_t) {
                 best_t = th;
@@ -597,7 +669,10 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
                 // coordinate reaching G) needs no term of its own: an axis that
                 // steps to G exits through plane(i, G), the very value t1 is
                 // the minimum of, so texit >= t1 already holds there.
-                stop = any_hit | (!kAnyHit & (best_t < texit)) | (texit >= t1);
+                // (a multi-hit walk: all kMulti entries before this cell's exit)
+                float near_t = best_t;
+                if constexpr (kMulti > 0) near_t = mh->t[kMulti - 1];
+                stop = any_hit | (!kAnyHit & (near_t < texit)) | (texit >= t1);
                 const uint32_t diff = (l0 ^ n0) | (l1 ^ n1) | (l2 ^ n2);
                 const uint32_t top = 31u - __builtin_clz(diff);  // highest flipped bit
                 t = texit;
@@ -635,6 +710,7 @@ __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, flo
         }
         if (any_hit) return true;
     }
+    if constexpr (kMulti > 0) return mh->ref[0] != kNoHit;
     if (!kAnyHit && best_ref != kNoHit) {
         tout = best_t;
         iout = best_ref;

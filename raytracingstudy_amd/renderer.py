@@ -400,6 +400,62 @@ class KernelRenderer:
         check(self._lib.rt_pick(self._h, float(u), float(v), ctypes.byref(h), _fptr(pt)), self._h)
         return h.sphere != _lib.RT_NO_HIT, float(h.t), int(h.sphere), pt
 
+    # -- ordered multi-hit queries (rt_trace_rays_multi / rt_pick_multi) -----------
+    def trace_rays_multi_device(self, rays_ptr: int, n: int, k: int, hits_ptr: int,
+                                counts_ptr: Optional[int] = None, stream: Optional[int] = None,
+                                stats: bool = False) -> Optional[RtStats]:
+        """rt_trace_rays_multi on buffers already on the GPU: n rt_ray at rays_ptr ->
+        n*k rt_hit at hits_ptr (ray-major, each ray's k nearest by (t, sphere
+        index), then {tmax, RT_NO_HIT} fillers) and n uint32 counts at counts_ptr
+        (optional).  Asynchronous on `stream` (None: the renderer's own) unless stats."""
+        st = RtStats() if stats else None
+        check(self._lib.rt_trace_rays_multi(self._h, ctypes.c_void_p(rays_ptr) if rays_ptr else None,
+                                            int(n), int(k),
+                                            ctypes.c_void_p(hits_ptr) if hits_ptr else None,
+                                            ctypes.c_void_p(counts_ptr) if counts_ptr else None,
+                                            ctypes.c_void_p(stream) if stream else None,
+                                            ctypes.byref(st) if st is not None else None), self._h)
+        return st
+
+    def trace_rays_multi(self, rays, k: int, stats: bool = False):
+        """The k nearest spheres along each ray of a host (n, 8) float32 array in
+        rt_ray layout: uploads, runs rt_trace_rays_multi, and returns
+        (t (n, k) float32, sphere (n, k) uint32, count (n,) uint32[, RtStats]).
+        Slots past a ray's count hold t = the ray's tmax and sphere = RT_NO_HIT."""
+        import torch
+        ra = np.ascontiguousarray(rays, np.float32)
+        if ra.ndim != 2 or ra.shape[1] != 8:
+            raise ValueError("rays must be an (n, 8) float32 array in rt_ray layout")
+        if not ra.flags.writeable:  # torch.from_numpy wants a writable array
+            ra = ra.copy()
+        n, k = ra.shape[0], int(k)
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_rays = torch.from_numpy(ra).to(dev)
+        d_hits = torch.empty((max(n, 1), max(k, 1), 2), dtype=torch.int32, device=dev)
+        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
+        st = self.trace_rays_multi_device(d_rays.data_ptr() if n else 0, n, k,
+                                          d_hits.data_ptr() if n else 0,
+                                          d_counts.data_ptr() if n else 0, None, stats)
+        self.synchronize()
+        hits = d_hits[:n].cpu().numpy()
+        t = np.ascontiguousarray(hits[:, :, 0]).view(np.float32)
+        sphere = np.ascontiguousarray(hits[:, :, 1]).view(np.uint32)
+        count = d_counts[:n].cpu().numpy().view(np.uint32)
+        return (t, sphere, count, st) if stats else (t, sphere, count)
+
+    def pick_multi(self, u: float, v: float, k: int):
+        """rt_pick_multi: the k nearest spheres under image coordinates (u, v) of the
+        current camera, front to back -> (count, t (k,) float32, sphere (k,) uint32);
+        slots past count hold +inf and RT_NO_HIT."""
+        k = int(k)
+        hits = (_lib.RtHit * max(k, 1))()
+        cnt = ctypes.c_uint32(0)
+        check(self._lib.rt_pick_multi(self._h, float(u), float(v), k, hits, ctypes.byref(cnt)), self._h)
+        t = np.array([hits[i].t for i in range(k)], np.float32)
+        sphere = np.array([hits[i].sphere for i in range(k)], np.uint32)
+        return int(cnt.value), t, sphere
+
     # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
     def render_gbuffer_device(self, hits_ptr: Optional[int] = None, normals_ptr: Optional[int] = None,
                               albedo_ptr: Optional[int] = None, stream: Optional[int] = None,

@@ -2,6 +2,7 @@
 """Ray-query throughput (rt_trace_rays) on a config's scene, coherent and incoherent rays.
 
     python tools/query_bench.py [--config c3] [--log2-rays 22] [--reps 20] [--warmup 3]
+                                [--multi K[,K...]]
 
 Two ray sets of 2^k rays each, nearest and any-hit, timed with HIP events around
 the launch on a stream (median of --reps launches after --warmup):
@@ -10,7 +11,11 @@ the launch on a stream (median of --reps launches after --warmup):
   incoherent  origins just off random spheres' surfaces, uniformly random
               directions (neighbouring lanes share nothing)
 Prints one JSON line: Mrays/s, hit fraction and the walk's work per ray (from
-one stats launch) for each set and kind.  Needs a GPU: there is no fallback.
+one stats launch) for each set and kind.  With --multi, also the ordered
+multi-hit query (rt_trace_rays_multi) for each K on the same two ray sets in
+the same process, next to the nearest query: ms, Mrays/s, the mean count per
+ray, nodes and tests per ray, and the ratios to one and to K nearest launches.
+Needs a GPU: there is no fallback.
 """
 from __future__ import annotations
 
@@ -65,7 +70,12 @@ def main():
     ap.add_argument("--log2-rays", type=int, default=22)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--multi", default="", metavar="K[,K...]",
+                    help="also time rt_trace_rays_multi for these k (1 .. 16)")
     args = ap.parse_args()
+    multi_ks = [int(x) for x in args.multi.split(",") if x]
+    if any(k < 1 or k > rt._lib.RT_MULTIHIT_MAX for k in multi_ks):
+        sys.exit(f"query_bench: --multi takes k in 1 .. {rt._lib.RT_MULTIHIT_MAX}")
     import torch
     if rt.device_count() == 0:
         sys.exit("query_bench: no HIP device visible (rates are measured on the GPU only)")
@@ -85,6 +95,25 @@ def main():
     out = {"config": args.config, "rays": n, "reps": args.reps, "warmup": args.warmup,
            "scene": {k: info[k] for k in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
                                           "cell_table_depth")}}
+
+    def timed(launch):
+        for _ in range(args.warmup):
+            launch()
+        ms = []
+        for _ in range(args.reps):
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            launch()
+            e1.record(stream)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return ms
+
+    d_mhits = d_counts = None
+    if multi_ks:
+        d_mhits = torch.empty((n, max(multi_ks), 2), dtype=torch.int32, device="cuda")
+        d_counts = torch.empty((n,), dtype=torch.int32, device="cuda")
     for name, rays in sets.items():
         d_rays = torch.from_numpy(rays).cuda()
         torch.cuda.synchronize()
@@ -92,17 +121,7 @@ def main():
             def launch():
                 r.trace_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), kind,
                                     stream=stream.cuda_stream)
-            for _ in range(args.warmup):
-                launch()
-            ms = []
-            for _ in range(args.reps):
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                launch()
-                e1.record(stream)
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
+            ms = timed(launch)
             st = r.trace_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), kind,
                                      stream=stream.cuda_stream, stats=True)
             hit = float((d_hits[:, 1] != -1).float().mean().item())
@@ -113,6 +132,24 @@ def main():
                 "nodes_per_ray": round(st.nodes_visited / n, 3),
                 "prims_per_ray": round(st.prims_tested / n, 3),
                 "stats_launch_ms": round(float(st.ms), 4)}
+        near = out[f"{name}_nearest"]["ms_median"]
+        for k in multi_ks:
+            def launch_multi():
+                r.trace_rays_multi_device(d_rays.data_ptr(), n, k, d_mhits.data_ptr(),
+                                          d_counts.data_ptr(), stream=stream.cuda_stream)
+            ms = timed(launch_multi)
+            st = r.trace_rays_multi_device(d_rays.data_ptr(), n, k, d_mhits.data_ptr(),
+                                           d_counts.data_ptr(), stream=stream.cuda_stream, stats=True)
+            med = float(np.median(ms))
+            out[f"{name}_multi{k}"] = {
+                "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                "Mrays_s": round(n / med / 1e3, 1),
+                "mean_count": round(float(d_counts.float().mean().item()), 4),
+                "nodes_per_ray": round(st.nodes_visited / n, 3),
+                "prims_per_ray": round(st.prims_tested / n, 3),
+                "stats_launch_ms": round(float(st.ms), 4),
+                "vs_nearest": round(med / near, 4),
+                "vs_k_nearest_launches": round(med / (k * near), 4)}
     print(json.dumps(out))
     r.close()
 
