@@ -57,7 +57,7 @@ void fill_frame_args(rt_renderer* r, FrameArgs& a) {
     // round 4: spp < 8 frames take the per-wave queue too (variant 4, no
     // workgroup barrier per block tile: C2 0.155 -> 0.107 ms,
     // profiles/r04/c2_waveq_ab.log)
-    a.variant = v ? v : (a.spp >= 8u ? kVariantWaveQ : kVariantWaveQLow);
+    a.variant = v ? v : default_variant(a.spp);
 }
 
 int check_tiles(rt_renderer* r, const uint32_t* ids, uint32_t n_tiles, uint32_t ts,
@@ -167,11 +167,9 @@ int frame_counters(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     a.wq_slots = nullptr;
     a.wq_slot_stride = 0;
     if (scene) {
-        const uint32_t nt = a.tiles ? a.n_tiles : 0u;
-        const uint32_t nsb = scene_superblocks(a.W, a.H, a.spp, nt, a.tile_size);
-        const uint32_t nbk = scene_blocks(a.W, a.H, a.spp, nt, a.tile_size);
-        a.wq_slot_shift = wave_queue_slot_shift(nsb, nbk);
-        a.wq_slot_stride = (a.wq_slot_shift == 12u ? nsb : nbk) + 2u;
+        const WaveGrid grid(a.W, a.H, a.spp, a.tiles ? a.n_tiles : 0u, a.tile_size);
+        a.wq_slot_shift = grid.slot_shift();
+        a.wq_slot_stride = (a.wq_slot_shift == 12u ? grid.superblocks() : grid.blocks()) + 2u;
         words += (8u * static_cast<size_t>(a.wq_slot_stride) + 1u) / 2u;
     }
     if (r->ctr_stride < words) {  // (re)allocate both sets and zero them
@@ -209,11 +207,8 @@ void counters_after_launch(rt_renderer* r, const FrameArgs& a, bool launched) {
 int superblock_order(rt_renderer* r, FrameArgs& a, hipStream_t) {
     a.sb_order = nullptr;
     if (r->cfg.mode != RT_MODE_SCENE || a.tiles || a.wq_slot_shift != 12u || !r->sb_hilbert) return RT_OK;
-    // the superblock grid of this frame (scene_body's nsx x nsy)
-    uint32_t spw, g, ppw, tw, th;
-    wave_tile_shape(a.spp, spw, g, ppw, tw, th);
-    const uint32_t gw = (a.W + tw - 1u) / tw, gh = (a.H + th - 1u) / th;
-    const uint32_t nx = ((gw + 7u) / 8u + 7u) / 8u, ny = ((gh + 7u) / 8u + 7u) / 8u;
+    const WaveGrid grid(a.W, a.H, a.spp, 0u, 0u);
+    const uint32_t nx = grid.nsx, ny = grid.nsy;  // the superblock grid of this frame
     if (r->sb_nx != nx || r->sb_ny != ny || !r->sb_order.p) {
         const std::vector<uint32_t> ord = hilbert_order(nx, ny);
         if (const int ost = ensure(r, r->sb_order, ord.size())) return ost;

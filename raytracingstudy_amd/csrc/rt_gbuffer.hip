@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(kBlockThreads) gbuffer_kernel(FrameArgs a, GBu
         gbuffer_get_ray(a.cam, static_cast<float>(x), static_cast<float>(y), d0, d1, d2);
         float t = __builtin_inff();  // a miss reports tmax
         uint32_t ref = kNoHit;
-        const bool hit = walk<false, 2, false, kStats, false, false, false, true>(
+        const bool hit = walk<GenericRay<false, kStats>>(
             a.sc, a.cam.o[0], a.cam.o[1], a.cam.o[2], d0, d1, d2, 0.0f, __builtin_inff(), t, ref,
             n_nodes, n_prims, stk);
         const size_t pix = static_cast<size_t>(y) * a.W + x;

@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(kBlockThreads) multihit_kernel(FrameArgs a, Mu
         mh.clear(r1.w);  // a free slot reports the ray's tmax
         float t_unused = 0.0f;
         uint32_t ref_unused = kNoHit;
-        walk<false, 2, false, kStats, false, false, false, true, K>(
+        walk<MultiHitRay<K, kStats>>(
             a.sc, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r0.w, r1.w, t_unused, ref_unused, n_nodes,
             n_prims, stk, false, nullptr, ~0u, &mh);
         uint2* out = q.hits + static_cast<size_t>(i) * q.k;

@@ -6,25 +6,16 @@
 #pragma once
 #include <stdint.h>
 
+#include "rt_sched.h"  // the scheduling constants: block size, variants, wave grid, LDS layout
+
 namespace rtamd {
 
-constexpr int kBlockThreads = 256;  // 4 waves of 64
 constexpr uint32_t kTileSide = 16;  // scene kernel: largest block tile (16x16 pixels per workgroup)
 constexpr uint32_t kMaxDepth = 16;  // octree depth limit (grid coordinates stay < 2^16, exact in f32)
 constexpr float kShadowEps = 1e-5f; // shadow-ray origin offset along the normal (world units)
 constexpr uint32_t kNoHit = 0xFFFFFFFFu;
 
-// scene kernel variants (rt_config.flags bits 16..19, RT_FLAG_VARIANT_SHIFT);
-// 0 picks 13 for spp >= 8, else 10.  Numbers of the variants measured and
-// removed are not reused.
-constexpr uint32_t kVariantLaneUnified = 7;   // one walk instance for primary + shadow, 2 in flight
-constexpr uint32_t kVariantLaneUnified2NoStats = 10; // spp < 8 default: 7 with counters only in stats frames
-constexpr uint32_t kVariantWaveQ = 13;     // unified walk scheduled per wave over per-XCD queues
-                                           // (default for spp >= 8)
-constexpr uint32_t kVariantWaveQLow = 4;   // the per-wave queue for spp < 8 too (no workgroup
-                                           // barrier per block tile; the spp < 8 default
-                                           // since round 4)
-// prim_sp padding after the last leaf list: the leaf loads run kChunk - 1 = 1
+// prim_sp padding after the last leaf list: the leaf loads run kLeafChunk - 1 = 1
 // sphere past a leaf's end (rt_capi.cpp fills it)
 constexpr uint32_t kPrimPad = 4;
 
@@ -77,7 +68,7 @@ enum BlockStat : uint32_t {
     kBsDescend,       // trips taking the record-descent path
     kBsInternal,      // descents into an internal child (continue)
     kBsLeaf,          // leaves entered
-    kBsLeafChunk,     // leaf chunk trips (kChunk spheres each)
+    kBsLeafChunk,     // leaf chunk trips (kLeafChunk spheres each)
     kBsTest,          // sphere tests (one per slot of a chunk)
     kBsSqrt,          // tests past h >= 0 (square root path)
     kBsAccept,        // tests returning a hit
@@ -103,56 +94,6 @@ enum BlockStat : uint32_t {
     kBsLdsLeaf,       // leaf visits staged through the wave's LDS buffer
     kBlockStats
 };
-
-// Wave mapping of the scene kernel: spw = min(spp, 64) samples of a pixel on
-// g = pow2ceil(spw) lanes, ppw = 64 / g pixels per wave as a tw x th tile.
-inline void wave_tile_shape(uint32_t spp, uint32_t& spw, uint32_t& g, uint32_t& ppw,
-                            uint32_t& tw, uint32_t& th) {
-    spw = spp >= 64u ? 64u : (spp ? spp : 1u);
-    g = 1;
-    while (g < spw) g *= 2u;
-    ppw = 64u / g;
-    uint32_t lg = 0;
-    while ((1u << lg) < ppw) ++lg;
-    tw = 1u << ((lg + 1) / 2);
-    th = 1u << (lg / 2);
-}
-
-// Superblocks (8x8 blocks of 8x8 wave tiles) of a scene frame's wave-tile
-// grid, or of n_tiles packed tiles.
-inline uint32_t scene_superblocks(uint32_t W, uint32_t H, uint32_t spp, uint32_t n_tiles,
-                                  uint32_t tile_size) {
-    uint32_t spw, g, ppw, tw, th;
-    wave_tile_shape(spp, spw, g, ppw, tw, th);
-    const uint32_t gw = n_tiles ? tile_size / tw : (W + tw - 1) / tw;
-    const uint32_t gh = n_tiles ? tile_size / th : (H + th - 1) / th;
-    const uint32_t nsx = ((gw + 7u) / 8u + 7u) / 8u, nsy = ((gh + 7u) / 8u + 7u) / 8u;
-    return (n_tiles ? n_tiles : 1u) * nsx * nsy;
-}
-
-// 8x8-wave-tile blocks of the same grid(s) that hold at least one wave tile.
-inline uint32_t scene_blocks(uint32_t W, uint32_t H, uint32_t spp, uint32_t n_tiles,
-                             uint32_t tile_size) {
-    uint32_t spw, g, ppw, tw, th;
-    wave_tile_shape(spp, spw, g, ppw, tw, th);
-    const uint32_t gw = n_tiles ? tile_size / tw : (W + tw - 1) / tw;
-    const uint32_t gh = n_tiles ? tile_size / th : (H + th - 1) / th;
-    return (n_tiles ? n_tiles : 1u) * ((gw + 7u) / 8u) * ((gh + 7u) / 8u);
-}
-
-// The wave queue's level-1 unit (scene_kernel): superblocks when there are
-// enough of them that one superblock is a small part of an XCD's share
-// (>= 192: C3 full frame (510), block slots cost it 0.6-3.4%; C4 8-way share
-// (255), equal within noise) and they are mostly wave
-// tiles (a packed 64x64 tile below 64 spp fills 1/4 of one or less), else
-// 8x8 blocks (1/8 and 1/4 C3 tile shares, 64 and 128: -4% and -2%,
-// profiles/r02/slot_size_ab.log).
-#ifndef RT_SLOT_SB_MIN
-#define RT_SLOT_SB_MIN 192u
-#endif
-inline uint32_t wave_queue_slot_shift(uint32_t superblocks, uint32_t blocks) {
-    return superblocks >= RT_SLOT_SB_MIN && 4ull * blocks >= 3ull * 64u * superblocks ? 12u : 6u;
-}
 
 // Pinhole camera (include/camera.h:9-56): K and R column-major like glm.
 struct CamArgs {
@@ -284,9 +225,6 @@ enum BinInfoWord : uint32_t {
 constexpr uint32_t kBinFlagCapacity = 1u;  // the entries do not fit the buffer
 constexpr uint32_t kBinFlagWide = 2u;      // the wide list overflowed
 constexpr uint32_t kBinFlagDense = 4u;     // mean list length over kBinMeanMax
-
-// Spheres per wave in the LDS leaf buffer (a leaf of >= kLeafBuf uses global loads)
-constexpr uint32_t kLeafBuf = 32;
 
 // Slack of the camera-relative screen, in units of 2^-24: the
 // screen may only pass MORE spheres than the exact test, so C' undercuts

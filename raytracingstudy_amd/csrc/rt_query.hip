@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(kBlockThreads) query_kernel(FrameArgs a, Query
         const float4 r1 = q.rays[2u * static_cast<size_t>(i) + 1u];
         float t = r1.w;  // a miss reports the ray's tmax
         uint32_t ref = kNoHit;
-        const bool hit = walk<kAny, 2, false, kStats, false, false, false, true>(
+        const bool hit = walk<GenericRay<kAny, kStats>>(
             a.sc, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r0.w, r1.w, t, ref, n_nodes, n_prims, stk);
         // the caller's sphere index, not the leaf reference
         const uint32_t sphere = hit ? a.sc.prim_idx[ref] : kNoHit;

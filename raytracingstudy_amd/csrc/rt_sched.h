@@ -1,0 +1,196 @@
+// rt_sched.h — how a scene frame is scheduled, stated once: which kernel
+// instance runs it (SceneInstance, Frame<>), its wave-tile grid (WaveGrid) and
+// its workgroup's LDS layout (FrameLds).  Scalars only and no HIP types, so it
+// compiles with g++ too (tests/native/sched_dump.cpp); rt_params.h includes it.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define RT_HD __host__ __device__
+#else
+#define RT_HD
+#endif
+
+namespace rtamd {
+
+constexpr int kBlockThreads = 256;  // 4 waves of 64
+
+// scene kernel variants (rt_config.flags bits 16..19, RT_FLAG_VARIANT_SHIFT);
+// 0 picks 13 for spp >= 8, else 4 (default_variant).  Numbers of the variants
+// measured and removed are not reused.
+constexpr uint32_t kVariantLaneUnified = 7;   // one walk instance for primary + shadow, 2 in flight
+constexpr uint32_t kVariantLaneUnified2NoStats = 10; // 7 with counters only in stats frames
+constexpr uint32_t kVariantWaveQ = 13;     // unified walk scheduled per wave over per-XCD queues
+                                           // (default for spp >= 8)
+constexpr uint32_t kVariantWaveQLow = 4;   // the per-wave queue for spp < 8 too (no workgroup
+                                           // barrier per block tile; the spp < 8 default
+                                           // since round 4)
+RT_HD inline uint32_t default_variant(uint32_t spp) { return spp >= 8u ? kVariantWaveQ : kVariantWaveQLow; }
+
+// Spheres per wave in the LDS leaf buffer (a leaf of >= kLeafBuf uses global loads)
+constexpr uint32_t kLeafBuf = 32;
+constexpr size_t kLeafBufBytes = (kBlockThreads / 64u) * kLeafBuf * 16u;  // float4 records
+
+// Sorted rounds (rt_sorted.h): up to 256 samples of one pixel per wave
+constexpr uint32_t kSortMaxRounds = 4;
+constexpr uint32_t kSortMax = 64u * kSortMaxRounds;
+// per wave: per sample a slot {t, sphere} -> {lam | miss g, albedo | miss b}
+// and a kind byte; the tracing order and the list of lit samples (u8 each)
+constexpr uint32_t kSortCellBits = 3;  // jitter cells per axis: 2^3 (8 x 8, Morton order)
+constexpr uint32_t kSortCells = 1u << (2u * kSortCellBits);
+constexpr uint32_t kSortWaveBytes = kSortMax * 8u + 3u * kSortMax + kSortCells * 4u;
+static_assert(kSortWaveBytes % 16u == 0u, "per-wave regions stay float4-aligned");
+
+// Per-thread ancestor-stack levels.  Internal nodes sit at depths <
+// stack_depth (the deepest leaf), and with a cell table only depths >= K are
+// pushed: K .. stack_depth - 1 (C5: its tree stops at depth 8 under a
+// depth-12 grid, so 2 levels, not 6).  The stackless walk (no_stack, sorted
+// pixels) keeps none when there is a table: an ancestor that is not the
+// current node re-enters through the table.
+RT_HD inline uint32_t stack_levels(uint32_t tab_k, uint32_t stack_depth, bool no_stack = false) {
+    if (no_stack && tab_k) return 0u;
+    const uint32_t sb = tab_k ? tab_k - 1u : 0u;
+    return stack_depth > 1u + sb ? stack_depth - 1u - sb : 1u;
+}
+
+// The workgroup's dynamic LDS, as byte offsets.  Block tiles and the plain
+// wave queue: the 256 pixel sums (float4, the leader lanes' slots), the
+// ancestor stacks [level][thread] (uint2), the per-wave leaf buffers.  Sorted
+// rounds: no per-thread pixel sums; the stacks first (the stackless walk's),
+// then each wave's colours and tracing order (kSortWaveBytes), then the leaf
+// buffers.
+struct FrameLds {
+    uint32_t sums, stacks, sort_waves, leaf_buf, bytes;  // (a region the layout lacks: empty)
+    RT_HD FrameLds(bool sorted, uint32_t tab_k, uint32_t stack_depth) {
+        sums = 0u;
+        stacks = sorted ? 0u : kBlockThreads * 16u;
+        sort_waves = stacks + stack_levels(tab_k, stack_depth, sorted) * kBlockThreads * 8u;
+        leaf_buf = sort_waves + (sorted ? (kBlockThreads / 64u) * kSortWaveBytes : 0u);
+        bytes = leaf_buf + static_cast<uint32_t>(kLeafBufBytes);
+    }
+};
+
+// Wave mapping of the scene kernel: spw = min(spp, 64) samples of a pixel on
+// g = pow2ceil(spw) lanes, ppw = 64 / g pixels per wave as a tw x th tile.
+RT_HD inline void wave_tile_shape(uint32_t spp, uint32_t& spw, uint32_t& g, uint32_t& ppw,
+                                  uint32_t& tw, uint32_t& th) {
+    spw = spp >= 64u ? 64u : (spp ? spp : 1u);
+    g = 1;
+    while (g < spw) g *= 2u;
+    ppw = 64u / g;
+    uint32_t lg = 0;
+    while ((1u << lg) < ppw) ++lg;
+    tw = 1u << ((lg + 1) / 2);
+    th = 1u << (lg / 2);
+}
+
+// The wave queue's level-1 unit (scene_body): superblocks when there are
+// enough of them that one superblock is a small part of an XCD's share
+// (>= 192: C3 full frame (510), block slots cost it 0.6-3.4%; C4 8-way share
+// (255), equal within noise) and they are mostly wave
+// tiles (a packed 64x64 tile below 64 spp fills 1/4 of one or less), else
+// 8x8 blocks (1/8 and 1/4 C3 tile shares, 64 and 128: -4% and -2%,
+// profiles/r02/slot_size_ab.log).
+#ifndef RT_SLOT_SB_MIN
+#define RT_SLOT_SB_MIN 192u
+#endif
+RT_HD inline uint32_t wave_queue_slot_shift(uint32_t superblocks, uint32_t blocks) {
+    return superblocks >= RT_SLOT_SB_MIN && 4ull * blocks >= 3ull * 64u * superblocks ? 12u : 6u;
+}
+
+// The wave-tile grid of a scene frame, or of each of n_tiles packed tiles
+// (n_tiles = 0: the frame): gw x gh wave tiles of tw x th pixels, numbered in
+// 8x8 blocks (nbx x nby, those that hold at least one wave tile) of 8x8-block
+// superblocks (nsx x nsy; one 64x64 tile at 64 spp).
+struct WaveGrid {
+    uint32_t tw, th, gw, gh, nbx, nby, nsx, nsy, grids;
+    RT_HD WaveGrid(uint32_t W, uint32_t H, uint32_t spp, uint32_t n_tiles, uint32_t tile_size) {
+        uint32_t spw, g, ppw;
+        wave_tile_shape(spp, spw, g, ppw, tw, th);
+        gw = n_tiles ? tile_size / tw : (W + tw - 1) / tw;
+        gh = n_tiles ? tile_size / th : (H + th - 1) / th;
+        nbx = (gw + 7u) / 8u, nby = (gh + 7u) / 8u;
+        nsx = (nbx + 7u) / 8u, nsy = (nby + 7u) / 8u;
+        grids = n_tiles ? n_tiles : 1u;
+    }
+    RT_HD uint64_t units() const { return static_cast<uint64_t>(grids) * gw * gh; }  // wave tiles
+    RT_HD uint32_t blocks() const { return grids * nbx * nby; }
+    RT_HD uint32_t superblocks() const { return grids * nsx * nsy; }
+    RT_HD uint32_t slot_shift() const { return wave_queue_slot_shift(superblocks(), blocks()); }
+};
+
+// ---------------------------------------------------------------------------
+// The scene-kernel instance a frame runs
+// ---------------------------------------------------------------------------
+
+// A compiled instance's switches, as one word: Frame<kFWaveQ | kFOcc | kFBin>.
+enum FrameFlag : uint32_t {
+    kFTiles = 1u << 0,   // renders a packed tile list, not the frame
+    kFStats = 1u << 1,   // counts rays, node visits and sphere tests
+    kFProg = 1u << 2,    // progressive: adds onto FrameArgs::accum
+    kFWaveQ = 1u << 3,   // the per-wave two-level queue (else the block-tile queue)
+    kFSorted = 1u << 4,  // quadrant-sorted rounds, one pixel per wave
+    kFOcc = 1u << 5,     // shadow rays answered from the occluder lists
+    kFBin = 1u << 6,     // primary rays answered from the frame's screen-space bins
+};
+
+template <uint32_t kF>
+struct Frame {
+    static constexpr bool tiles = kF & kFTiles, stats = kF & kFStats, prog = kF & kFProg,
+                          waveq = kF & kFWaveQ, sorted = kF & kFSorted, occ = kF & kFOcc,
+                          bin = kF & kFBin;
+    // waves per SIMD asked of the register allocator: plain wave-queue frames
+    // are the 8-wave build (scene_kernel_w8), stats frames keep 7
+    static constexpr int min_waves = waveq ? (stats ? 7 : 8) : 1;
+    // unsorted wave-queue walks screen by the 8-byte image-plane records and
+    // stage no leaves; the block-tile queue keeps the staged 16-byte screen
+    static constexpr bool cam8 = waveq && !sorted;
+    static_assert(!sorted || waveq, "sorted rounds: a wave-queue frame");
+    static_assert(!occ || !stats, "stats frames walk: their counters are the oracle's");
+    static_assert(!bin || (!stats && waveq), "bins: plain frames of the wave queue");
+};
+
+struct SceneInstance {
+    bool valid;  // false: a variant this build does not have
+    bool waveq, stats, prog, sorted, occ, bin;
+    RT_HD uint32_t flags() const {  // without kFTiles: the launcher's
+        return (stats ? kFStats : 0u) | (prog ? kFProg : 0u) | (waveq ? kFWaveQ : 0u) |
+               (sorted ? kFSorted : 0u) | (occ ? kFOcc : 0u) | (bin ? kFBin : 0u);
+    }
+    RT_HD uint32_t min_waves() const { return waveq ? (stats ? 7u : 8u) : 1u; }
+    RT_HD bool w8() const { return waveq && !stats; }  // scene_kernel_w8: the instances that read bins
+};
+
+// The instance of a frame.  count_work: a stats frame; sort_on: false only
+// under the test hook RT_SORT=0; have_occ: the scene has occluder lists, the
+// frame casts shadows and its camera is inside their gate; have_bins: the
+// frame built bins.  Sorted rounds: a wave-queue frame of one pixel per wave
+// and 2..4 rounds, wherever the per-wave LDS still lets 8 workgroups share a
+// CU.  Progressive frames run the unified walk whatever the variant: the wave
+// queue from 8 spp, like variant 13.
+RT_HD inline SceneInstance pick_scene_instance(uint32_t variant, uint32_t spp, bool progressive,
+                                               bool count_work, bool sort_on, bool have_occ,
+                                               bool have_bins, uint32_t tab_k, uint32_t stack_depth) {
+    if (!variant) variant = default_variant(spp);
+    SceneInstance s = {true, false, count_work, progressive, false, false, false};
+    const uint32_t rounds = (spp + 63u) / 64u;
+    s.sorted = sort_on && spp >= 64u && rounds >= 2u && rounds <= kSortMaxRounds &&
+               FrameLds(true, tab_k, stack_depth).bytes * 8u <= 160u * 1024u &&
+               (progressive || variant == kVariantWaveQ);
+    if (s.sorted)
+        s.waveq = true;
+    else if (progressive)
+        s.waveq = spp >= 8u;
+    else if (variant == kVariantWaveQ || variant == kVariantWaveQLow)
+        s.waveq = true;
+    else if (variant == kVariantLaneUnified)
+        s.stats = true;  // block-tile queue, counting in every frame
+    else if (variant != kVariantLaneUnified2NoStats)
+        s.valid = false;
+    s.occ = !s.stats && have_occ;
+    s.bin = !s.stats && s.waveq && have_bins;
+    return s;
+}
+
+}  // namespace rtamd

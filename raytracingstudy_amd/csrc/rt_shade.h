@@ -1,0 +1,258 @@
+// rt_shade.h — a frame's samples: the sample mapping and its hashes, the
+// camera ray, one sample's colour (sample_color_unified) and a wave tile's
+// pixels with their ordered sums (shade_wave_tile).  Device code of the scene
+// kernels; included by rt_kernels.hip only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rt_params.h"
+#include "rt_walk.h"  // the octree walk (shared with the ray-query kernels)
+#include "rt_bins.h"  // primary rays from the frame's screen-space bins
+
+namespace rtamd {
+
+__device__ __forceinline__ float sat(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+__device__ __forceinline__ float u01(uint32_t x) {
+    return static_cast<float>(x >> 8) * (1.0f / 16777216.0f);
+}
+
+// include/camera.h:24-41 — Camera::getRay, camera passed by value.
+__device__ __forceinline__ void get_ray(const CamArgs& c, float u, float v, float& wx, float& wy,
+                                        float& wz) {
+    const float dx = (u - c.K[2]) / c.K[0];
+    const float dy = (v - c.K[5]) / c.K[4];
+    const float dz = 1.0f;
+    wx = c.R[0] * dx + c.R[3] * dy + c.R[6] * dz;
+    wy = c.R[1] * dx + c.R[4] * dy + c.R[7] * dz;
+    wz = c.R[2] * dx + c.R[5] * dy + c.R[8] * dz;
+    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
+    wx /= len;
+    wy /= len;
+    wz /= len;
+}
+
+// ---------------------------------------------------------------------------
+// Frame mapping, shading, ordered accumulation
+//
+// A wave owns `ppw` pixels x `spw` samples (host: spw = min(spp, 64),
+// ppw = pow2floor(64 / spw)); lane l works on pixel l / spw, sample
+// round * spw + l % spw.  At spp >= 64 all 64 lanes of a wave trace jittered
+// samples of ONE pixel: their primary rays stay within one pixel footprint and
+// their shadow rays start from nearly the same point with the same direction,
+// so the wave's lanes follow nearly the same octree path (little SIMD
+// divergence, and coherent packets).  The per-pixel mean keeps the oracle's
+// exact summation order: every lane parks its sample colour in LDS and the
+// pixel's leader lane adds them in sample order.
+// ---------------------------------------------------------------------------
+
+struct PixelOut {
+    float r, g, b;
+};
+
+__device__ __forceinline__ uint32_t pack_rgba8(const PixelOut& p) {
+    const uint32_t r = static_cast<uint32_t>(sat(p.r) * 255.0f);
+    const uint32_t g = static_cast<uint32_t>(sat(p.g) * 255.0f);
+    const uint32_t b = static_cast<uint32_t>(sat(p.b) * 255.0f);
+    return r | (g << 8) | (b << 16) | (255u << 24);
+}
+
+// Unified lane path: one walk instance run twice (primary, then the shadow ray
+// of the lanes that need one), so the register allocator sees one walk.
+// kBin: the primary ray is answered from the frame's screen-space bins
+// (rt_bins.h; (tox, toy): the wave tile's origin pixel, wave-uniform); a tile
+// whose bin is over the cap, or a frame whose builder raised its flag, walks
+// under a wave-uniform branch.
+// C: the frame's switches (Frame<>, rt_sched.h).
+template <class C>
+__device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uint32_t x,
+                                                         uint32_t y, uint32_t hp, uint32_t s,
+                                                         bool valid, uint32_t& n_shadow,
+                                                         uint32_t& n_nodes, uint32_t& n_prims,
+                                                         void* stk, uint32_t* bs, uint32_t lbs,
+                                                         uint32_t tox = 0, uint32_t toy = 0) {
+    constexpr bool kStats = C::stats, kCam8 = C::cam8, kOcc = C::occ, kBin = C::bin;
+    const SceneArgs& S = a.sc;
+    KernArgs* ka = kernargs();
+    float u = static_cast<float>(x), v = static_cast<float>(y);
+    if (ka->jitter) {
+        u = u + u01(mix32(hp ^ (s << 1)));
+        v = v + u01(mix32(hp ^ ((s << 1) | 1u)));
+    }
+    float r0 = ka->cam.o[0], r1 = ka->cam.o[1], r2 = ka->cam.o[2];
+    float d0, d1, d2;
+    {
+        CamArgs cam;
+        for (int i = 0; i < 9; ++i) cam.K[i] = ka->cam.K[i], cam.R[i] = ka->cam.R[i];
+        get_ray(cam, u, v, d0, d1, d2);
+    }
+    const float miss_g = sat(d1), miss_b = sat(d2);
+    bool active = valid, hit0 = false;
+    float lam = 0.0f;
+    uint32_t al = 0;
+    uint2 occ_hdr = make_uint2(0u, 0u);  // kOcc: the hit sphere's occluder-list header
+    // the primary and the shadow walk as two instances (the phase loop was
+    // always unrolled into two copies; written out so that the primary one
+    // keeps the camera-relative screen, a compile-time choice)
+#pragma unroll
+    for (int phase = 0; phase < 2; ++phase) {
+        float t = 0.0f;
+        uint32_t idx = 0;
+        bool hit = false;
+        bool binned = false;
+        if (kBin && phase == 0) {
+            uint2 bh;
+            binned = !bin_header(tox, toy, bh);
+            if (binned)
+                hit = bin_nearest(bh, tox, toy, kernargs()->tw, kernargs()->th, active, r0, r1, r2, d0,
+                                  d1, d2, t, idx);
+        }
+        if (active && !binned) {
+            RT_BS(kBsPhase);
+            if (phase) RT_BS(kBsPhaseShadow);
+            if (phase == 0)
+                hit = walk<FramePrimary<kStats, kCam8>>(S, r0, r1, r2, d0, d1, d2, 0.0f, INFINITY, t, idx,
+                                                        n_nodes, n_prims, static_cast<uint2*>(stk),
+                                                        false, bs, lbs);
+            else if (kOcc) {
+                // answered from the hit sphere's occluder list (round 7)
+                hit = shadow_occluded<false>(S, occ_hdr, true, r0, r1, r2, static_cast<uint2*>(stk));
+            } else {
+                // the shadow direction L is the frame's, the same in every
+                // lane: read afresh from the kernel arguments (SGPRs), not the
+                // lanes' d registers
+                KernArgs* kl = kernargs();
+                hit = walk<FrameShadow<kStats>>(
+                    S, r0, r1, r2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, t, idx, n_nodes,
+                    n_prims, static_cast<uint2*>(stk), true, bs);
+            }
+        }
+        if (phase == 0) {
+            hit0 = active && hit;
+            bool want_shadow = false;
+            KernArgs* kb = kernargs();
+            if (hit0) {
+                RT_BS(kBsShadeLoad);  // the sphere record
+                RT_BS(kBsShadeLoad);  // the albedo
+                const float4 sp = kb->sc.prim_sp[idx];
+                const float p0 = r0 + t * d0;
+                const float p1 = r1 + t * d1;
+                const float p2 = r2 + t * d2;
+                const float ir = 1.0f / sp.w;
+                const float n0 = (p0 - sp.x) * ir;
+                const float n1 = (p1 - sp.y) * ir;
+                const float n2 = (p2 - sp.z) * ir;
+                const float ndl = n0 * kb->L[0] + n1 * kb->L[1] + n2 * kb->L[2];
+                lam = ndl > 0.0f ? ndl : 0.0f;
+                want_shadow = ndl > 0.0f && kb->shadows;
+                al = kb->sc.prim_al[idx];
+                if (kOcc && want_shadow) occ_hdr = kb->sc.prim_occ[idx];
+                r0 = p0 + n0 * kShadowEps;
+                r1 = p1 + n1 * kShadowEps;
+                r2 = p2 + n2 * kShadowEps;
+                d0 = kb->L[0];
+                d1 = kb->L[1];
+                d2 = kb->L[2];
+            }
+            active = want_shadow;
+            n_shadow += static_cast<uint32_t>(__popcll(__ballot(active)));  // wave-uniform
+            if (!__any(active)) break;
+        } else if (active && hit) {
+            lam = 0.0f;
+        }
+    }
+    PixelOut c{200.0f / 255.0f, miss_g, miss_b};
+    if (hit0) {
+        const float amb = kernargs()->ambient;
+        const float f = amb + (1.0f - amb) * lam;
+        c.r = static_cast<float>(al & 0xFFu) * (1.0f / 255.0f) * f;
+        c.g = static_cast<float>((al >> 8) & 0xFFu) * (1.0f / 255.0f) * f;
+        c.b = static_cast<float>((al >> 16) & 0xFFu) * (1.0f / 255.0f) * f;
+    }
+    return c;
+}
+
+// Wave tile (tw x th pixels x spw samples, launch_scene) at pixel origin
+// (ox, oy); for a packed tile list also obase: image pixel (x, y) of this
+// tile is packed word obase + y * tile_size + x (mod 2^32; one value kept
+// live across the walks instead of the slot and the tile-local origin).
+// Rounds of spw samples, pairwise butterfly per round, rounds added in
+// order in the leader's LDS slot, then the mean is written.
+template <class C>
+__device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc, void* stk,
+                                                uint32_t ox, uint32_t oy, uint32_t obase,
+                                                uint32_t& n_primary,
+                                                uint32_t& n_shadow, uint32_t& n_nodes,
+                                                uint32_t& n_prims, uint32_t* bs, uint32_t lbs) {
+    constexpr bool kTiles = C::tiles, kProg = C::prog;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t spw = a.spw, g = a.g;
+    const uint32_t pix = lane / g, sub = lane & (g - 1u);
+    const uint32_t qx = pix % a.tw, qy = pix / a.tw;
+    const uint32_t x = ox + qx, y = oy + qy;
+    const bool lane_pix = pix < a.ppw && x < a.W && y < a.H;
+    const bool leader = lane_pix && sub == 0;
+    const uint32_t pid = y * a.W + x;
+    const uint32_t hp = mix32(a.seedmix ^ pid);
+    // progressive: the stored sum seeds the leader's LDS slot, so round 0
+    // adds onto it like any later round (nothing extra live in the walk)
+    if (kProg && a.accum_in && leader) acc[threadIdx.x] = a.accum[(size_t)y * a.W + x];
+    // sample index across accumulated frames: s_base + r*spw + sub
+    const uint32_t s_base = kProg ? a.s_base : 0u;
+    const uint32_t sub_base = s_base + sub;
+    const uint32_t s_end = s_base + a.spp;
+    const bool lane_ok = lane_pix && sub < spw;
+    for (uint32_t r = 0; r < a.rounds; ++r) {
+        const uint32_t sg = r * spw + sub_base;
+        const bool valid = lane_ok && sg < s_end;
+        n_primary += static_cast<uint32_t>(__popcll(__ballot(valid)));  // wave-uniform
+        PixelOut c = sample_color_unified<C>(a, x, y, hp, sg, valid, n_shadow, n_nodes, n_prims, stk,
+                                             bs, lbs, ox, oy);
+        // Pixel sum of this round: pairwise butterfly over the pixel's g
+        // lanes (missing samples are 0) = oracle.c:tree_sum; rounds are then
+        // added in order in the leader's LDS slot.
+        if (!valid) c = PixelOut{0.0f, 0.0f, 0.0f};
+        for (uint32_t m = 1; m < g; m <<= 1) {
+            c.r += __shfl_xor(c.r, static_cast<int>(m), 64);
+            c.g += __shfl_xor(c.g, static_cast<int>(m), 64);
+            c.b += __shfl_xor(c.b, static_cast<int>(m), 64);
+        }
+        if (leader) {
+            if (r || (kProg && a.accum_in)) {
+                const float4 A = acc[threadIdx.x];
+                c.r = A.x + c.r;
+                c.g = A.y + c.g;
+                c.b = A.z + c.b;
+            }
+            acc[threadIdx.x] = make_float4(c.r, c.g, c.b, 0.0f);
+        }
+    }
+    // outputs: fields read afresh (kernargs()), not kept live across the walks
+    KernArgs* ko = kernargs();
+    if (leader) {
+        const float4 A = acc[threadIdx.x];
+        if (kProg) ko->accum[(size_t)y * ko->W + x] = A;
+        const float isp = ko->inv_spp;
+        const PixelOut p{A.x * isp, A.y * isp, A.z * isp};
+        const uint32_t rgba = pack_rgba8(p);
+        if (kTiles) {
+            ko->out8[obase + y * ko->tile_size + x] = rgba;
+        } else {
+            ko->out8[(size_t)y * ko->W + x] = rgba;
+            if (ko->out32) ko->out32[(size_t)y * ko->W + x] = make_float4(p.r, p.g, p.b, 1.0f);
+        }
+    } else if (kTiles && sub == 0 && pix < ko->ppw) {
+        ko->out8[obase + y * ko->tile_size + x] = 0u;  // off-image pixel of an edge tile
+    }
+}
+
+}  // namespace rtamd

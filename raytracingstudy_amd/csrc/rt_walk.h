@@ -100,15 +100,6 @@ __device__ __forceinline__ void frame_failed() {
     __hip_atomic_store(ka->qerr, ka->frame_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-constexpr uint32_t kSortMaxRounds = 4;  // up to 256 samples per pixel
-constexpr uint32_t kSortMax = 64u * kSortMaxRounds;
-// per wave: per sample a slot {t, sphere} -> {lam | miss g, albedo | miss b}
-// and a kind byte; the tracing order and the list of lit samples (u8 each)
-constexpr uint32_t kSortCellBits = 3;  // jitter cells per axis: 2^3 (8 x 8, Morton order)
-constexpr uint32_t kSortCells = 1u << (2u * kSortCellBits);
-constexpr uint32_t kSortWaveBytes = kSortMax * 8u + 3u * kSortMax + kSortCells * 4u;
-static_assert(kSortWaveBytes % 16u == 0u, "per-wave regions stay float4-aligned");
-
 // rank of this lane among the lanes set in m
 __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
@@ -130,24 +121,16 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
 // / +0.3 / +0.1%, 8: C3 +3.5%, C5 +4.6%
 // (profiles/r06/ab_r6_lmin2_lmin3_lmin4_lmin5.log, ab_r6_lmin4_lmin8.log).
 constexpr uint32_t kLdsLeafMin = 5;
-constexpr size_t kLeafBufBytes = (kBlockThreads / 64u) * kLeafBuf * sizeof(float4);
 
-// Ancestor-stack levels per thread: depths 1..D-1, or K..D-1 with a cell table
-// (a pop above depth K jumps through the table instead).
-// Per-thread ancestor-stack levels.  Internal nodes sit at depths <
-// stack_depth (the deepest leaf), and with a cell table only depths >= K are
-// pushed: K .. stack_depth - 1 (C5: its tree stops at depth 8 under a
-// depth-12 grid, so 2 levels, not 6).  The stackless walk (kNoStack, sorted
-// pixels) keeps none when there is a table: an ancestor that is not the
-// current node re-enters through the table.
+// Ancestor-stack levels per thread (rt_sched.h) of a scene
 __host__ __device__ inline uint32_t stack_levels(const SceneArgs& S, bool no_stack = false) {
-    if (no_stack && S.tab_k) return 0u;
-    const uint32_t sb = S.tab_k ? S.tab_k - 1u : 0u;
-    return S.stack_depth > 1u + sb ? S.stack_depth - 1u - sb : 1u;
+    return stack_levels(S.tab_k, S.stack_depth, no_stack);
 }
 
-// First float4 of this wave's LDS leaf buffer (the layout of scene_lds_bytes
-// and sort_lds_bytes).
+// First float4 of this wave's LDS leaf buffer: FrameLds::leaf_buf / 16
+// (rt_sched.h, the layout's one statement) plus the wave's part, written in
+// float4 units here because computed from FrameLds' byte offsets the kernels
+// get other scalar instructions than the ones measured (profiles/r13).
 __device__ __forceinline__ uint32_t leaf_buf_base(const SceneArgs& S, bool sorted) {
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t head = sorted ? (stack_levels(S, true) * kBlockThreads * 8u +
@@ -245,15 +228,56 @@ struct MultiHits {
 // the stop rule.  isect keeps the ray's own tmax, so a sphere tied with the
 // last entry at a lower index is still seen.  Returns whether mh holds a hit;
 // tout and iout are left alone.
-template <bool kAnyHitT, int kChunk = 2, bool kDynAny = false, bool kStats = true,
-          bool kNoStack = false, bool kShadowL = false, bool kCam8 = false, bool kGeneric = false,
-          int kMulti = 0>
+//
+// Leaf spheres are read kLeafChunk = 2 at a time, in every walk: one dwordx4
+// of 8-byte screen records a chunk.  (4 a chunk in the shadow walks: 4 spills
+// of 48-100 B, C3 +6%, C5 +8%, C5d +5%, profiles/r06/ab_shd_chunk4.log.)
+constexpr int kLeafChunk = 2;
+
+// The switches of a walk, by name; the kinds of walk that exist follow.
+struct WalkKind {
+    static constexpr bool any_hit = false;   // kAnyHitT: compile-time any-hit
+    static constexpr bool dyn_any = false;   // kDynAny: any-hit or nearest by `any_rt`
+    static constexpr bool stats = false;     // counts node visits and sphere tests
+    static constexpr bool no_stack = false;  // kNoStack: no ancestor stack where there is a table
+    static constexpr bool shadow_l = false;  // kShadowL: any-hit rays along the frame's L
+    static constexpr bool cam8 = false;      // kCam8: 8-byte image-plane screen, no staging
+    static constexpr bool generic = false;   // kGeneric: a caller's ray, no frame
+    static constexpr int multi = 0;          // kMulti: keeps the k nearest hits
+};
+// a frame's primary walk (staged 16-byte screen, or kCam8: the image-plane
+// screen) and its shadow walk along L
+template <bool kStats, bool kCam8>
+struct FramePrimary : WalkKind { static constexpr bool stats = kStats, cam8 = kCam8; };
+template <bool kStats>
+struct FrameShadow : WalkKind { static constexpr bool any_hit = true, stats = kStats, shadow_l = true; };
+// the sorted path's primary and shadow walks: stackless, any-hit or nearest
+// at run time (kDynAny), as measured
+template <bool kStats>
+struct SortedPrimary : WalkKind { static constexpr bool dyn_any = true, stats = kStats, no_stack = true, cam8 = true; };
+template <bool kStats>
+struct SortedShadow : WalkKind { static constexpr bool dyn_any = true, stats = kStats, no_stack = true, shadow_l = true; };
+// the occluder lists' fallback: a shadow walk of a plain frame
+template <bool kNoStack>
+struct OccFallback : WalkKind { static constexpr bool any_hit = true, no_stack = kNoStack, shadow_l = true; };
+// a caller's ray, any-hit or nearest (rt_query.hip, rt_gbuffer.hip), or
+// keeping its K nearest hits (rt_multihit.hip)
+template <bool kAny, bool kStats>
+struct GenericRay : WalkKind { static constexpr bool any_hit = kAny, stats = kStats, generic = true; };
+template <int K, bool kStats>
+struct MultiHitRay : GenericRay<false, kStats> { static constexpr int multi = K; };
+
+template <class Kind>
 __device__ __forceinline__ bool walk(const SceneArgs& S, float o0, float o1, float o2, float d0,
                                      float d1, float d2, float tmin, float tmax, float& tout,
                                      uint32_t& iout, uint32_t& n_nodes, uint32_t& n_prims,
                                      uint2* __restrict__ stk, bool any_rt = false,
                                      uint32_t* bs = nullptr, uint32_t lb_u = ~0u,
-                                     MultiHits<kMulti>* mh = nullptr) {
+                                     MultiHits<Kind::multi>* mh = nullptr) {
+    constexpr bool kAnyHitT = Kind::any_hit, kDynAny = Kind::dyn_any, kStats = Kind::stats,
+                   kNoStack = Kind::no_stack, kShadowL = Kind::shadow_l, kCam8 = Kind::cam8,
+                   kGeneric = Kind::generic;
+    constexpr int kChunk = kLeafChunk, kMulti = Kind::multi;
     static_assert(!kShadowL || kAnyHitT || kDynAny, "a shadow walk along L is an any-hit walk");
     static_assert(!kGeneric || (!kShadowL && !kCam8), "a generic ray has no frame to screen against");
     static_assert(kMulti == 0 || (kGeneric && !kAnyHitT && !kDynAny),
@@ -728,7 +752,7 @@ __device__ __forceinline__ bool shadow_walk_fallback(const SceneArgs& S, float o
     KernArgs* kl = kernargs();
     float ts;
     uint32_t is, nn = 0, np = 0;
-    return walk<true, 2, false, false, kNoStack, true>(
+    return walk<OccFallback<kNoStack>>(
         S, o0, o1, o2, kl->L[0], kl->L[1], kl->L[2], 0.0f, INFINITY, ts, is, nn, np, stk, true);
 }
 

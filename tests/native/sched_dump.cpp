@@ -1,0 +1,51 @@
+// Prints csrc/rt_sched.h's results (tests/test_sched_cpu.py).  The command is
+// argv[1]; each line of standard input is one row of decimal arguments, each
+// line of output that row's result.
+//   pick  variant spp progressive count_work sort_on have_occ have_bins tab_k stack_depth
+//         -> valid waveq stats prog sorted occ bin min_waves w8 flags
+//   grid  W H spp n_tiles tile_size
+//         -> tw th gw gh nbx nby nsx nsy blocks superblocks units slot_shift
+//   lds   sorted tab_k stack_depth
+//         -> sums stacks sort_waves leaf_buf bytes
+#include <cstdio>
+#include <cstring>
+
+#include "../../raytracingstudy_amd/csrc/rt_sched.h"
+
+using namespace rtamd;
+
+// the instance flags name the switches they say they do
+static_assert(Frame<kFTiles | kFStats | kFProg>::tiles && Frame<kFStats>::stats && Frame<kFProg>::prog &&
+                  !Frame<kFStats | kFProg>::tiles && !Frame<kFStats>::waveq,
+              "Frame<> decodes its flags");
+static_assert(Frame<kFWaveQ | kFOcc | kFBin>::min_waves == 8 && Frame<kFWaveQ | kFStats>::min_waves == 7 &&
+                  Frame<kFOcc>::min_waves == 1,
+              "waves per SIMD follow the queue and the counters");
+static_assert(Frame<kFWaveQ>::cam8 && !Frame<kFWaveQ | kFSorted>::cam8 && !Frame<0u>::cam8,
+              "the image-plane screen: unsorted wave-queue walks");
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    char line[256];
+    while (fgets(line, sizeof(line), stdin)) {
+        unsigned v[9] = {};
+        const int n = sscanf(line, "%u %u %u %u %u %u %u %u %u", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6,
+                             v + 7, v + 8);
+        if (!strcmp(argv[1], "pick") && n == 9) {
+            const SceneInstance s = pick_scene_instance(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]);
+            printf("%d %d %d %d %d %d %d %u %d %u\n", s.valid, s.waveq, s.stats, s.prog, s.sorted, s.occ,
+                   s.bin, s.min_waves(), s.w8(), s.flags());
+        } else if (!strcmp(argv[1], "grid") && n == 5) {
+            const WaveGrid g(v[0], v[1], v[2], v[3], v[4]);
+            printf("%u %u %u %u %u %u %u %u %u %u %llu %u\n", g.tw, g.th, g.gw, g.gh, g.nbx, g.nby, g.nsx, g.nsy,
+                   g.blocks(), g.superblocks(), static_cast<unsigned long long>(g.units()), g.slot_shift());
+        } else if (!strcmp(argv[1], "lds") && n == 3) {
+            const FrameLds l(v[0] != 0u, v[1], v[2]);
+            printf("%u %u %u %u %u\n", l.sums, l.stacks, l.sort_waves, l.leaf_buf, l.bytes);
+        } else {
+            fprintf(stderr, "sched_dump: bad command or row: %s %s", argv[1], line);
+            return 2;
+        }
+    }
+    return 0;
+}

@@ -2,7 +2,7 @@
 """Instruction budget of one kernel from its gfx950 assembly.
 
     make -C raytracingstudy_amd/csrc asm          # -> raytracingstudy_amd/csrc/rt_kernels.s
-    python tools/isa_budget.py [--kernel scene_kernel_w8ILb0ELb0ELb0E] [--asm path]
+    python tools/isa_budget.py [--kernel scene_kernel_w8INS_5FrameILj8EEEE] [--asm path]
 
 Splits the kernel's body into basic blocks and counts, per block, the
 instructions by issue class:
@@ -98,7 +98,7 @@ def parse(asm_path: str, kernel_sub: str):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", default=os.path.join(ROOT, "raytracingstudy_amd", "csrc", "rt_kernels.s"))
-    ap.add_argument("--kernel", default="scene_kernel_w8ILb0ELb0ELb0E")
+    ap.add_argument("--kernel", default="scene_kernel_w8INS_5FrameILj8EEEE")
     ap.add_argument("--groups", default="",
                     help="name=first:last,... sums of block ranges (inclusive, in layout order)")
     ap.add_argument("--ops", action="store_true", help="also list each block's opcodes")
