@@ -40,6 +40,8 @@
  *     could report)
  *   (none: one colour per pixel,                          rt_render_gbuffer
  *     src/renderer.cu:57-82)
+ *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
+ *     the octree which spheres touch a ball)
  *   (none: no error reporting, all void)                  rt_last_error
  *
  * Threading: one handle per host thread / stream; calls on one handle are not
@@ -447,6 +449,51 @@ int rt_trace_rays_multi(rt_renderer* r, const void* dev_rays, uint32_t n, uint32
  * dev_hits above; count_out (may be NULL) as dev_counts.  The Displayer's
  * repeated click on one spot walks down this list. */
 int rt_pick_multi(rt_renderer* r, float u, float v, uint32_t k, rt_hit* hits_out, uint32_t* count_out);
+
+/* ---- sphere-overlap queries ------------------------------------------------ */
+/* Which scene spheres touch this ball: the contacts of a simulation's spheres
+ * after a step, the Displayer's brush selection ("everything within 5 cm of the
+ * picked point"), point containment (radius 0).  The reference has no
+ * counterpart (Octree::traverse is a stub, include/octree.h:19-21).
+ * For one probe (p, R) the accepted set is every scene sphere (c, r) with
+ * d2 <= s * s, where dx = p.x - c.x (likewise dy, dz), d2 = (dx*dx + dy*dy) +
+ * dz*dz and s = R + r: all f32, in that order, no contraction.  The test is
+ * closed (tangent spheres touch); R = 0 is point containment; a probe with a
+ * non-finite component or R < 0 has an empty set; each sphere counts once,
+ * however many octree leaves list it.
+ *   dev_probes   n rt_probe in device memory.
+ *   dev_indices  n*k uint32, probe-major: probe i's slots [i*k, i*k + k) hold
+ *                the k smallest sphere indices of its set, ascending; slots
+ *                past those hold RT_NO_HIT.  Every slot is written.
+ *   dev_counts   n uint32 or NULL: min(k, size of the set), with
+ *                RT_OVERLAP_MORE OR-ed in iff the set is larger than k (exact).
+ * flags: RT_OVERLAP_SKIP_SELF leaves sphere index i out of probe i's set (a
+ * probe with i >= n_spheres skips nothing): as rt_probe has a scene sphere's
+ * layout, the scene's own device sphere list as the probes with this flag is
+ * "all contacts of the scene".
+ * stream, ordering and stats as rt_trace_rays: asynchronous unless stats !=
+ * NULL, ordered after the handle's earlier work; primary_rays = shadow_rays =
+ * 0, nodes_visited = node records the query read, prims_tested = predicate
+ * evaluations, ms = device time of the launch.  k == 0, k > RT_OVERLAP_MAX,
+ * unknown flag bits, or a NULL dev_probes / dev_indices with n > 0:
+ * RT_E_INVALID.  n == 0: RT_OK, nothing launched.  No scene: RT_E_NOSCENE.
+ * Reads scene state only: it never changes a frame; a multi-device handle
+ * answers from devices[0]. */
+typedef struct rt_probe {
+    float center[3];
+    float radius;
+} rt_probe; /* 16 bytes: the layout of a scene sphere */
+#define RT_OVERLAP_MAX 16
+#define RT_OVERLAP_MORE 0x80000000u /* in a count word: the accepted set is larger than k */
+enum { RT_OVERLAP_SKIP_SELF = 1u }; /* probe i does not report sphere index i */
+int rt_query_overlaps(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_t k, uint32_t flags,
+                      void* dev_indices, void* dev_counts, void* stream, rt_stats* stats);
+/* A one-probe query that waits for the answer, like rt_pick.  indices_out has
+ * room for k uint32, filled as dev_indices above; count_out (may be NULL) as
+ * dev_counts.  The point rt_pick returns goes here for a brush selection
+ * (INTEGRATION.md). */
+int rt_overlaps_at(rt_renderer* r, const float center[3], float radius, uint32_t k,
+                   uint32_t* indices_out, uint32_t* count_out);
 
 /* ---- first-hit G-buffer --------------------------------------------------- */
 /* The per-pixel geometry of the frame the current size and camera would

@@ -176,6 +176,25 @@ public:
         check(rt_pick_multi(r_, u, v, k, hits, &count), r_);
         return count;
     }
+    // the scene spheres each probe sphere touches (rt_query_overlaps): n rt_probe
+    // -> n*k sphere indices, probe-major, the k smallest ascending, and n count
+    // words (or null; RT_OVERLAP_MORE: the set is larger), all in device memory;
+    // 1 <= k <= RT_OVERLAP_MAX; flags RT_OVERLAP_SKIP_SELF
+    void queryOverlaps(const void* dev_probes, uint32_t n, uint32_t k, void* dev_indices,
+                       void* dev_counts = nullptr, uint32_t flags = 0, void* stream = nullptr,
+                       rt_stats* stats = nullptr) {
+        check(rt_query_overlaps(r_, dev_probes, n, k, flags, dev_indices, dev_counts, stream, stats), r_);
+    }
+    // the scene spheres within `radius` of a point, e.g. a brush around pick()'s
+    // point (rt_overlaps_at); returns how many of indices[0 .. k) are spheres,
+    // *more (may be null): the set is larger than k
+    uint32_t overlapsAt(const float center[3], float radius, uint32_t k, uint32_t* indices,
+                        bool* more = nullptr) {
+        uint32_t count = 0;
+        check(rt_overlaps_at(r_, center, radius, k, indices, &count), r_);
+        if (more) *more = (count & RT_OVERLAP_MORE) != 0;
+        return count & ~RT_OVERLAP_MORE;
+    }
     // first-hit G-buffer of the current camera (rt_render_gbuffer): W*H rt_hit,
     // float[4] normals and packed RGBA8 albedo in device memory, each optional
     void renderGBuffer(void* dev_hits, void* dev_normals = nullptr, void* dev_albedo = nullptr,

@@ -279,6 +279,9 @@ int rt_destroy(rt_renderer* r) {
     r->q_hit.release();
     r->q_multi_hits.release();
     r->q_multi_count.release();
+    r->q_probe.release();
+    r->q_overlap_idx.release();
+    r->q_overlap_count.release();
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();

@@ -860,6 +860,70 @@ int rt_pick_multi(rt_renderer* r, float u, float v, uint32_t k, rt_hit* hits_out
     return RT_OK;
 }
 
+// Sphere-overlap queries: the scene spheres each probe sphere
+// touches, the k smallest indices.  A query like rt_trace_rays: scene state
+// only, the query path's own stat lines, the same stream ordering.
+int rt_query_overlaps(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_t k, uint32_t flags,
+                      void* dev_indices, void* dev_counts, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_query_overlaps: null handle");
+    if (k == 0 || k > RT_OVERLAP_MAX)
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: k must be 1 .. RT_OVERLAP_MAX");
+    if (flags & ~static_cast<uint32_t>(RT_OVERLAP_SKIP_SELF))
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: unknown flag bits");
+    if (n > 0 && (!dev_probes || !dev_indices))
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: null buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_query_overlaps: no scene (rt_set_scene first)");
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    int st;
+    if ((st = set_device(r))) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    // the kernel's leading argument is a FrameArgs (rt_overlap.hip): the scene, the rest zero
+    FrameArgs a;
+    memset(&a, 0, sizeof(a));
+    a.sc = r->sc;
+    const float slack_m = overlap_slack_m(r->info.root_min, r->info.root_max);
+    unsigned long long* ctr = nullptr;
+    if (stats && (st = query_stats_begin(r, hs, ctr))) return st;
+    hipError_t e = launch_overlap(a, dev_probes, dev_indices, dev_counts, n, k,
+                                  (flags & RT_OVERLAP_SKIP_SELF) != 0, slack_m, ctr, hs);
+    if (e != hipSuccess) return hip_fail(r, e, "rt_query_overlaps: kernel launch");
+    if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
+    if ((st = mark_queued(r, hs))) return st;
+    if (stats && (st = query_stats_read(r, ctr, stats))) return st;  // (no rays: both ray counts 0)
+    return RT_OK;
+}
+
+int rt_overlaps_at(rt_renderer* r, const float center[3], float radius, uint32_t k,
+                   uint32_t* indices_out, uint32_t* count_out) {
+    if (!r || !center || !indices_out) return fail(r, RT_E_INVALID, "rt_overlaps_at: null argument");
+    if (k == 0 || k > RT_OVERLAP_MAX)
+        return fail(r, RT_E_INVALID, "rt_overlaps_at: k must be 1 .. RT_OVERLAP_MAX");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_overlaps_at: no scene (rt_set_scene first)");
+    const float4 probe = make_float4(center[0], center[1], center[2], radius);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q_probe, 1)) || (st = ensure(r, r->q_overlap_idx, RT_OVERLAP_MAX)) ||
+        (st = ensure(r, r->q_overlap_count, 1)))
+        return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q_probe.p, &probe, sizeof(probe), hipMemcpyHostToDevice, hs));
+    if ((st = rt_query_overlaps(r, r->q_probe.p, 1, k, 0, r->q_overlap_idx.p, r->q_overlap_count.p, hs,
+                                nullptr)))
+        return st;
+    uint32_t idx[RT_OVERLAP_MAX], count = 0;
+    RT_HIP(r, hipMemcpyAsync(idx, r->q_overlap_idx.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipMemcpyAsync(&count, r->q_overlap_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    memcpy(indices_out, idx, k * sizeof(uint32_t));
+    if (count_out) *count_out = count;
+    return RT_OK;
+}
+
 // First-hit G-buffer (the reference writes one colour per pixel,
 // src/renderer.cu:57-82).  Like a query it reads scene and camera state only:
 // no frame id, no fill_frame_args (which advances both), the query path's own

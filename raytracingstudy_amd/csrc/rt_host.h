@@ -19,6 +19,7 @@
 #include "../../include/rt.h"
 #include "octree_gpu.h"
 #include "rt_bins_math.h"
+#include "rt_overlap_math.h"
 #include "rt_params.h"
 #include "scene_build.h"
 
@@ -48,6 +49,12 @@ hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32
 // counts (may be null) against a.sc; 1 <= k <= RT_MULTIHIT_MAX; counters != null: a stats launch
 hipError_t launch_multihit(const FrameArgs& a, const void* rays, void* hits, void* counts, uint32_t n,
                            uint32_t k, unsigned long long* counters, hipStream_t st);
+// rt_overlap.hip: n probes (rt_probe) -> n x k sphere indices (probe-major, the k smallest of each
+// probe's accepted set, ascending) and n count words (may be null) against a.sc; 1 <= k <=
+// RT_OVERLAP_MAX; slack_m: overlap_slack_m of the root box; counters != null: a stats launch
+hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices, void* counts,
+                          uint32_t n, uint32_t k, bool skip_self, float slack_m,
+                          unsigned long long* counters, hipStream_t st);
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
@@ -338,6 +345,10 @@ struct RendererState {
     // rt_pick_multi's hits (up to RT_MULTIHIT_MAX) and its count
     DevBuf<uint2> q_multi_hits;
     DevBuf<uint32_t> q_multi_count;
+    // rt_overlaps_at's probe, its indices (up to RT_OVERLAP_MAX) and its count word
+    DevBuf<float4> q_probe;
+    DevBuf<uint32_t> q_overlap_idx;
+    DevBuf<uint32_t> q_overlap_count;
     rt_scene_info info{};
     std::string err;
     // multi-device handle (rt_create_multi): this renderer is devices[0]'s

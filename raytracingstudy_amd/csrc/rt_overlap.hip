@@ -1,0 +1,242 @@
+// rt_overlap.hip — sphere-overlap queries (rt_query_overlaps, rt_overlaps_at;
+// include/rt.h): for each probe sphere, the k smallest indices
+// of the scene spheres it touches, and whether there are more.  The reference
+// has no counterpart (Octree::traverse is a stub, include/octree.h:19-21).
+//
+// One probe per lane in a box-guided depth-first descent of the octree
+// records: a cell is visited iff it meets the probe's grown box
+// (rt_overlap_math.h), a leaf's spheres are tested with the exact predicate.
+// Compiled like rt_query.hip (-ffp-contract=off).
+#include <hip/hip_runtime.h>
+
+#include "rt_overlap_math.h"
+#include "rt_params.h"
+#include "rt_walk.h"
+
+namespace rtamd {
+
+struct OverlapArgs {
+    const float4* probes;          // n x {centre.xyz, radius}
+    uint32_t* indices;             // n x k sphere indices | kNoHit, probe-major
+    uint32_t* counts;              // n x {min(k, |set|) | kOverlapMore}, or null
+    uint32_t n;
+    uint32_t k;                    // the caller's k: 1 <= k <= K
+    uint32_t skip_self;            // probe i leaves sphere index i out
+    uint32_t levels;               // the LDS stack's levels (the launcher sized it)
+    float slack_m;                 // overlap_slack_m of the scene's root box
+    unsigned long long* counters;  // stats launches: 8 lines of kStatLineStride words
+};
+
+constexpr uint32_t kOverlapMore = 0x80000000u;  // RT_OVERLAP_MORE
+
+__device__ __forceinline__ unsigned long long overlap_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// One lane's K smallest accepted sphere indices, ascending, a free slot
+// kNoHit (which sorts after every index).  `more`: a sphere that is not held
+// was turned away from a full buffer, or an entry was pushed out, so the set
+// is larger than K.  Every index below is a compile-time constant once the
+// loops are unrolled: the array is registers, never scratch.
+template <int K>
+struct OverlapSet {
+    uint32_t idx[K];
+    bool more;
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < K; ++i) idx[i] = kNoHit;
+        more = false;
+    }
+    __device__ __forceinline__ void offer(uint32_t ci) {
+        if (ci > idx[K - 1]) {  // (the last slot is taken, or ci could not exceed it)
+            more = true;
+            return;
+        }
+        uint32_t pos = 0;  // entries that sort before the candidate
+        bool held = false;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            pos += idx[i] < ci ? 1u : 0u;
+            held |= idx[i] == ci;
+        }
+        if (held) return;  // met again in another leaf
+        more |= idx[K - 1] != kNoHit;
+#pragma unroll
+        for (int i = K - 1; i >= 0; --i) {
+            const bool below = static_cast<uint32_t>(i) > pos;  // shifts down one slot
+            const bool here = static_cast<uint32_t>(i) == pos;
+            const int up = i > 0 ? i - 1 : 0;
+            idx[i] = here ? ci : below ? idx[up] : idx[i];
+        }
+    }
+};
+
+// The children of the cell at corner l (finest-grid units) and half-size
+// `half` that the box meets: per axis the lower half iff lo < mid, the upper
+// iff hi >= mid; child c's bits are x = 1, y = 2, z = 4.
+__device__ __forceinline__ uint32_t children_met(const OverlapBox& b, uint32_t l0, uint32_t l1,
+                                                 uint32_t l2, uint32_t half) {
+    const float m0 = static_cast<float>(l0 + half);  // integers <= 2^16: exact
+    const float m1 = static_cast<float>(l1 + half);
+    const float m2 = static_cast<float>(l2 + half);
+    const uint32_t x = (b.lo[0] < m0 ? 0x55u : 0u) | (b.hi[0] >= m0 ? 0xAAu : 0u);
+    const uint32_t y = (b.lo[1] < m1 ? 0x33u : 0u) | (b.hi[1] >= m1 ? 0xCCu : 0u);
+    const uint32_t z = (b.lo[2] < m2 ? 0x0Fu : 0u) | (b.hi[2] >= m2 ? 0xF0u : 0u);
+    return x & y & z;
+}
+
+// One probe per lane, 256-thread blocks, the K-entry buffer in registers (K is
+// the caller's k rounded up to a compiled size).  A probe is one coalesced
+// dwordx4 load.  FrameArgs leads the argument block as in rt_query.hip.  The
+// dynamic LDS is the per-lane descent stack, [level][thread]: level d holds
+// the node at depth d while the lane is below it: {first child slot, valid |
+// leaf << 8 | children still to visit << 16}.
+template <int K, bool kStats>
+__global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, OverlapArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    uint2* stk = reinterpret_cast<uint2*>(lds) + threadIdx.x;
+    const uint32_t i = blockIdx.x * kBlockThreads + threadIdx.x;
+    uint32_t n_nodes = 0, n_prims = 0;
+    if (i < q.n) {
+        const SceneArgs& S = a.sc;
+        const float4 p = q.probes[i];
+        OverlapSet<K> set;
+        set.clear();
+        const uint32_t self = q.skip_self ? i : kNoHit;
+        const float4* __restrict__ prim_sp = S.prim_sp;
+        const uint32_t* __restrict__ prim_idx = S.prim_idx;
+        // A leaf's spheres in list order, kLeafChunk loads in flight; a slot
+        // past the leaf's end reads the next leaf or the kPrimPad tail (in
+        // bounds) and is never tested.  prim_idx is read for accepted ones only.
+        auto leaf = [&](uint32_t off, uint32_t cnt) {
+            static_assert(kLeafChunk <= static_cast<int>(kPrimPad) + 1, "leaf loads may run past a leaf");
+            for (uint32_t j = 0; j < cnt; j += kLeafChunk) {
+                float4 sv[kLeafChunk];
+#pragma unroll
+                for (int s = 0; s < kLeafChunk; ++s) sv[s] = prim_sp[off + j + s];
+#pragma unroll
+                for (int s = 0; s < kLeafChunk; ++s) {
+                    if (j + s < cnt) {
+                        if (kStats) n_prims += 1;
+                        if (overlap_accepts(p.x, p.y, p.z, p.w, sv[s].x, sv[s].y, sv[s].z, sv[s].w)) {
+                            const uint32_t ci = prim_idx[off + j + s];
+                            if (ci != self) set.offer(ci);
+                        }
+                    }
+                }
+            }
+        };
+        if (overlap_probe_ok(p.x, p.y, p.z, p.w)) {
+            const OverlapBox b = overlap_box(p.x, p.y, p.z, p.w, S.rmin, S.scale, q.slack_m);
+            const bool in_root = b.lo[0] < S.G && b.lo[1] < S.G && b.lo[2] < S.G && b.hi[0] >= 0.0f &&
+                                 b.hi[1] >= 0.0f && b.hi[2] >= 0.0f;
+            if (in_root) {
+                if (kStats) n_nodes += 1;  // the root record
+                if (S.root_is_leaf) {
+                    if (S.root.y) leaf(S.root.x, S.root.y);  // an empty scene's root holds 0
+                } else {
+                    // the node the lane iterates: its record, depth, corner and
+                    // size, and the children still to visit (a mask that only
+                    // loses bits: no child is visited twice)
+                    uint2 node = S.root;
+                    uint32_t depth = 0, l0 = 0, l1 = 0, l2 = 0, size = 1u << S.max_depth;
+                    uint32_t rem = children_met(b, l0, l1, l2, size >> 1) & node.y & 0xFFu;
+                    for (;;) {
+                        if (rem == 0u) {
+                            if (depth == 0u) break;
+                            depth -= 1;
+                            size <<= 1;
+                            l0 &= ~(size - 1u);
+                            l1 &= ~(size - 1u);
+                            l2 &= ~(size - 1u);
+                            node = stk[depth * kBlockThreads];
+                            rem = node.y >> 16;
+                            continue;
+                        }
+                        const uint32_t c = static_cast<uint32_t>(__builtin_ctz(rem));
+                        rem &= rem - 1u;
+                        const uint32_t valid = node.y & 0xFFu;
+                        const uint2 rec = S.nodes[node.x + __builtin_popcount(valid & ((1u << c) - 1u))];
+                        if (kStats) n_nodes += 1;
+                        if ((node.y >> 8) & (1u << c)) {
+                            leaf(rec.x, rec.y);
+                        } else if (depth < q.levels) {  // (always: the stack holds every internal depth)
+                            stk[depth * kBlockThreads] = make_uint2(node.x, (node.y & 0xFFFFu) | (rem << 16));
+                            const uint32_t half = size >> 1;
+                            l0 += (c & 1u) ? half : 0u;
+                            l1 += (c & 2u) ? half : 0u;
+                            l2 += (c & 4u) ? half : 0u;
+                            size = half;
+                            depth += 1;
+                            node = rec;
+                            rem = children_met(b, l0, l1, l2, size >> 1) & node.y & 0xFFu;
+                        }
+                    }
+                }
+            }
+        }
+        uint32_t* out = q.indices + static_cast<size_t>(i) * q.k;
+        uint32_t held = 0;
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            held += set.idx[s] != kNoHit ? 1u : 0u;
+            if (static_cast<uint32_t>(s) < q.k) out[s] = set.idx[s];
+        }
+        if (q.counts) {
+            const bool more = set.more || held > q.k;
+            q.counts[i] = min(held, q.k) | (more ? kOverlapMore : 0u);
+        }
+    }
+    if (kStats) {
+        // rt_query.hip's layout: words 2 and 3 of one line per XCD group
+        const unsigned long long s2 = overlap_wave_sum(n_nodes);
+        const unsigned long long s3 = overlap_wave_sum(n_prims);
+        if ((threadIdx.x & 63u) == 0) {
+            unsigned long long* c = q.counters + (blockIdx.x & 7u) * kStatLineStride;
+            atomicAdd(c + 2, s2);
+            atomicAdd(c + 3, s3);
+        }
+    }
+}
+
+template <int K>
+static void launch_k(const FrameArgs& a, const OverlapArgs& q, dim3 grid, size_t lds, hipStream_t st) {
+    if (q.counters) hipLaunchKernelGGL((overlap_kernel<K, true>), grid, dim3(kBlockThreads), lds, st, a, q);
+    else hipLaunchKernelGGL((overlap_kernel<K, false>), grid, dim3(kBlockThreads), lds, st, a, q);
+}
+
+// a.sc is the scene; the rest of `a` is unused by the kernel.  1 <= k <= 16
+// (the caller checked); counts may be null; slack_m: overlap_slack_m of the
+// scene's root box; counters != null: a stats launch (the caller zeroed its 8
+// lines).
+hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices, void* counts,
+                          uint32_t n, uint32_t k, bool skip_self, float slack_m,
+                          unsigned long long* counters, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (k == 0 || k > 16u) return hipErrorInvalidValue;
+    OverlapArgs q;
+    q.probes = static_cast<const float4*>(probes);
+    q.indices = static_cast<uint32_t*>(indices);
+    q.counts = static_cast<uint32_t*>(counts);
+    q.n = n;
+    q.k = k;
+    q.skip_self = skip_self ? 1u : 0u;
+    // one level per depth that can hold an internal node, from the deepest
+    // leaf itself (SceneArgs::stack_depth), not from stack_levels(): that one
+    // shrinks with the cell table, which this descent does not enter through
+    q.levels = a.sc.stack_depth ? a.sc.stack_depth : 1u;
+    q.slack_m = slack_m;
+    q.counters = counters;
+    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlockThreads - 1u) / kBlockThreads));
+    const size_t lds = static_cast<size_t>(q.levels) * kBlockThreads * sizeof(uint2);
+    if (k == 1) launch_k<1>(a, q, grid, lds, st);
+    else if (k == 2) launch_k<2>(a, q, grid, lds, st);
+    else if (k <= 4) launch_k<4>(a, q, grid, lds, st);
+    else if (k <= 8) launch_k<8>(a, q, grid, lds, st);
+    else launch_k<16>(a, q, grid, lds, st);
+    return hipGetLastError();
+}
+
+}  // namespace rtamd

@@ -456,6 +456,67 @@ class KernelRenderer:
         sphere = np.array([hits[i].sphere for i in range(k)], np.uint32)
         return int(cnt.value), t, sphere
 
+    # -- sphere-overlap queries (rt_query_overlaps / rt_overlaps_at) ----------------
+    def query_overlaps_device(self, probes_ptr: int, n: int, k: int, indices_ptr: int,
+                              counts_ptr: Optional[int] = None, skip_self: bool = False,
+                              stream: Optional[int] = None, stats: bool = False) -> Optional[RtStats]:
+        """rt_query_overlaps on buffers already on the GPU: n rt_probe (16 bytes each:
+        centre, radius; a scene sphere's layout) at probes_ptr -> n*k uint32 at
+        indices_ptr (probe-major, the k smallest sphere indices each probe touches,
+        ascending, then RT_NO_HIT fillers) and n count words at counts_ptr
+        (optional; RT_OVERLAP_MORE set: the probe touches more than k).
+        Asynchronous on `stream` (None: the renderer's own) unless stats."""
+        st = RtStats() if stats else None
+        check(self._lib.rt_query_overlaps(self._h, ctypes.c_void_p(probes_ptr) if probes_ptr else None,
+                                          int(n), int(k),
+                                          _lib.RT_OVERLAP_SKIP_SELF if skip_self else 0,
+                                          ctypes.c_void_p(indices_ptr) if indices_ptr else None,
+                                          ctypes.c_void_p(counts_ptr) if counts_ptr else None,
+                                          ctypes.c_void_p(stream) if stream else None,
+                                          ctypes.byref(st) if st is not None else None), self._h)
+        return st
+
+    def query_overlaps(self, probes, k: int, skip_self: bool = False, stats: bool = False):
+        """The scene spheres each probe of a host (n, 4) float32 array (centre xyz,
+        radius) touches: uploads, runs rt_query_overlaps, and returns
+        (indices (n, k) uint32, count (n,) uint32, more (n,) bool[, RtStats]).
+        Slots past a probe's count hold RT_NO_HIT; more: it touches more than k."""
+        import torch
+        pa = np.ascontiguousarray(probes, np.float32)
+        if pa.ndim != 2 or pa.shape[1] != 4:
+            raise ValueError("probes must be an (n, 4) float32 array in rt_probe layout")
+        if not pa.flags.writeable:  # torch.from_numpy wants a writable array
+            pa = pa.copy()
+        n, k = pa.shape[0], int(k)
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_probes = torch.from_numpy(pa).to(dev)
+        d_idx = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int32, device=dev)
+        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
+        st = self.query_overlaps_device(d_probes.data_ptr() if n else 0, n, k,
+                                        d_idx.data_ptr() if n else 0,
+                                        d_counts.data_ptr() if n else 0, skip_self, None, stats)
+        self.synchronize()
+        indices = d_idx[:n].cpu().numpy().view(np.uint32)
+        words = d_counts[:n].cpu().numpy().view(np.uint32)
+        count = words & np.uint32(~_lib.RT_OVERLAP_MORE & 0xFFFFFFFF)
+        more = (words & np.uint32(_lib.RT_OVERLAP_MORE)) != 0
+        return (indices, count, more, st) if stats else (indices, count, more)
+
+    def overlaps_at(self, center, radius: float, k: int):
+        """rt_overlaps_at: the scene spheres within `radius` of a point (a brush
+        around pick()'s point; radius 0: the spheres that contain it) ->
+        (count, indices (k,) uint32, more: bool); slots past count hold RT_NO_HIT."""
+        k = int(k)
+        c = np.ascontiguousarray(np.asarray(center, np.float32).reshape(3))
+        idx = (ctypes.c_uint32 * max(k, 1))()
+        cnt = ctypes.c_uint32(0)
+        check(self._lib.rt_overlaps_at(self._h, _fptr(c), float(radius), k, idx, ctypes.byref(cnt)),
+              self._h)
+        word = int(cnt.value)
+        return (word & ~_lib.RT_OVERLAP_MORE, np.array([idx[i] for i in range(k)], np.uint32),
+                bool(word & _lib.RT_OVERLAP_MORE))
+
     # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
     def render_gbuffer_device(self, hits_ptr: Optional[int] = None, normals_ptr: Optional[int] = None,
                               albedo_ptr: Optional[int] = None, stream: Optional[int] = None,
