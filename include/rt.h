@@ -297,6 +297,17 @@ int rt_get_bin_info(rt_renderer* r, rt_bin_info* info);
  * the next bin's first entry); indices_out `entries` sphere indices;
  * wide_out `wide` sphere indices.  Any may be NULL. */
 int rt_export_bins(rt_renderer* r, uint32_t* headers_out, uint32_t* indices_out, uint32_t* wide_out);
+/* The last frame's tile words, under rt_export_bins'
+ * state rules: that frame's wave tile is *tw x *th pixels (1x1 at 64 spp and
+ * more, up to 8x8 at 1 spp), a bin holds *tiles_per_bin = (8 / tw) * (8 / th)
+ * of them, and words_out[b * tiles_per_bin + ((y & 7) / th) * (8 / tw) +
+ * (x & 7) / tw] is the word of the wave tile that holds pixel (x, y) of bin b:
+ * bit k is set iff the bin's entry k (rt_export_bins' order) may be met by a
+ * sample of that tile; the frame's kernel tests those entries only.  The
+ * words of an empty bin and of a bin over the cap are 0.  words_out: bins *
+ * tiles_per_bin words, or NULL for the three sizes alone (any may be NULL). */
+int rt_export_bin_tiles(rt_renderer* r, uint32_t* tw, uint32_t* th, uint32_t* tiles_per_bin,
+                        uint64_t* words_out);
 /* Synthetic scene generator: splitmix64 -> PCG32 from `seed`;
  * centres U[0,1.28)^3, radius 0.02*(1000/n)^(1/3)*U[0.5,1), albedo U[0.2,1). */
 int rt_generate_spheres(uint32_t n, uint32_t seed, float* spheres_out, uint32_t* albedo_out);

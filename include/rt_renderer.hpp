@@ -207,6 +207,17 @@ public:
         check(rt_get_scene_info(r_, &i), r_);
         return i;
     }
+    // the last frame's tile words (rt_export_bin_tiles): bins * tiles-per-bin
+    // words, and that frame's wave tile in pixels
+    std::vector<uint64_t> exportBinTiles(uint32_t* tw = nullptr, uint32_t* th = nullptr) {
+        rt_bin_info bi;
+        uint32_t tpb = 0;
+        check(rt_get_bin_info(r_, &bi), r_);
+        check(rt_export_bin_tiles(r_, tw, th, &tpb, nullptr), r_);
+        std::vector<uint64_t> words(static_cast<size_t>(bi.bins) * tpb);
+        check(rt_export_bin_tiles(r_, nullptr, nullptr, nullptr, words.data()), r_);
+        return words;
+    }
     void readback(uint8_t* host_rgba8, float* host_rgba32f = nullptr) {
         check(rt_readback(r_, host_rgba8, host_rgba32f), r_);
     }

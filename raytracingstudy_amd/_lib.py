@@ -242,6 +242,7 @@ SIGNATURES = {
     "rt_export_occluders": (_int, [_P, _P, _P, _P, _P]),
     "rt_get_bin_info": (_int, [_P, ctypes.POINTER(RtBinInfo)]),
     "rt_export_bins": (_int, [_P, _P, _P, _P]),
+    "rt_export_bin_tiles": (_int, [_P, _P, _P, _P, _P]),
     "rt_save_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32]),
     "rt_load_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32, ctypes.POINTER(_u32)]),
     "rt_generate_spheres": (_int, [_u32, _u32, _P, _P]),

@@ -143,4 +143,46 @@ RT_BINS_HD inline BinRect sphere_screen_rect(const float sp[4], const float K[9]
     return out;
 }
 
+// ---- tile words ----
+// A frame's wave tiles are tw x th pixels (1x1 .. 8x8, powers of two, aligned
+// to their size), so a bin holds (8 / tw) * (8 / th) of them.  Every wave tile
+// of a non-empty bin within the cap gets one 64-bit word: bit k is set iff the
+// bin-local rectangle of the bin's sorted entry k overlaps the tile.  The
+// frame kernel visits the set bits only (rt_bins.h).
+
+RT_BINS_HD inline uint32_t bin_tiles_per_bin(uint32_t tw, uint32_t th) {
+    return (kBinSide / tw) * (kBinSide / th);
+}
+
+// The tile of pixel (x, y) within its bin, row-major; the table's index is
+// bin * bin_tiles_per_bin + this.
+RT_BINS_HD inline uint32_t bin_tile_index(uint32_t x, uint32_t y, uint32_t tw, uint32_t th) {
+    return ((y & (kBinSide - 1u)) / th) * (kBinSide / tw) + (x & (kBinSide - 1u)) / tw;
+}
+
+// The same from the sides' logarithms (tw = 1 << ltw, th = 1 << lth), as the
+// frame kernel computes it: no division.
+RT_BINS_HD inline uint32_t bin_tile_index_log2(uint32_t x, uint32_t y, uint32_t ltw, uint32_t lth) {
+    return (((y & (kBinSide - 1u)) >> lth) << (kBinShift - ltw)) + ((x & (kBinSide - 1u)) >> ltw);
+}
+
+// Whether an entry's rectangle (x0 | x1 << 4 | y0 << 8 | y1 << 12, bin-local,
+// inclusive: BinEntry::rect) holds a pixel of tile `tile` of its bin.
+RT_BINS_HD inline bool bin_rect_overlaps_tile(uint32_t rect, uint32_t tile, uint32_t tw, uint32_t th) {
+    const uint32_t per_row = kBinSide / tw;
+    const uint32_t tx0 = (tile % per_row) * tw, ty0 = (tile / per_row) * th;
+    const uint32_t tx1 = tx0 + tw - 1u, ty1 = ty0 + th - 1u;
+    return !((rect & 15u) > tx1 || ((rect >> 4) & 15u) < tx0 || ((rect >> 8) & 15u) > ty1 ||
+             ((rect >> 12) & 15u) < ty0);
+}
+
+// The word of tile `tile` over a list's rectangles in list order (cnt <= 64).
+RT_BINS_HD inline uint64_t bin_tile_word(const uint32_t* rects, uint32_t cnt, uint32_t tile, uint32_t tw,
+                                         uint32_t th) {
+    uint64_t w = 0;
+    for (uint32_t k = 0; k < cnt && k < 64u; ++k)
+        if (bin_rect_overlaps_tile(rects[k], tile, tw, th)) w |= uint64_t(1) << k;
+    return w;
+}
+
 }  // namespace rtamd

@@ -333,6 +333,7 @@ bool camera_in_occluder_gate(const rt_renderer* r, const FrameArgs& a) {
 int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     a.bin_hdr = nullptr;
     a.bin_ent = nullptr;
+    a.bin_nb = 0;
     a.bin_wide = nullptr;
     a.bin_info = nullptr;
     a.bin_nbx = 0;
@@ -382,7 +383,8 @@ int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     }
     if ((ost = ensure(r, r->bin_rects, std::max(1u, r->n_spheres))) ||
         (ost = ensure(r, r->bin_cnt, 2ull * nb + 1ull)) || (ost = ensure(r, r->bin_offs, nb + 1ull)) ||
-        (ost = ensure(r, r->bin_hdr, nb)) || (ost = ensure(r, r->bin_wide, 2ull * kBinWideCap)) ||
+        (ost = ensure(r, r->bin_hdr, size_t(nb) * (1u + kBinCap))) ||  // (and the tile words)
+        (ost = ensure(r, r->bin_wide, 2ull * kBinWideCap)) ||
         (ost = ensure(r, r->bin_info, kBinInfoWords)))
         return ost;
     if (r->bin_temp_items < nb + 1u || !r->bin_temp.p) {
@@ -402,6 +404,11 @@ int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     b.H = a.H;
     b.nbx = nbx;
     b.nby = nby;
+    {  // the wave tile launch_scene gives this frame's kernel
+        const WaveGrid grid(a.W, a.H, a.spp, a.tiles ? a.n_tiles : 0u, a.tile_size);
+        b.tw = grid.tw;
+        b.th = grid.th;
+    }
     b.shrink = r->bin_shrink;
     b.capacity = static_cast<uint32_t>(r->bin_ent.n / 2);
     b.cap = r->bin_cap;
@@ -413,6 +420,7 @@ int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     b.offs = r->bin_offs.p;
     b.hdr = r->bin_hdr.p;
     b.ent = r->bin_ent.p;
+    b.tiles = reinterpret_cast<unsigned long long*>(r->bin_hdr.p + nb);
     b.wide = r->bin_wide.p;
     b.info = r->bin_info.p;
     b.mirror = r->bin_mirror_dev;
@@ -430,8 +438,11 @@ int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     r->bin_last_capacity = b.capacity;
     r->bin_nbx = nbx;
     r->bin_nby = nby;
+    r->bin_tw = b.tw;
+    r->bin_th = b.th;
     a.bin_hdr = r->bin_hdr.p;
     a.bin_ent = r->bin_ent.p;
+    a.bin_nb = nb;
     a.bin_wide = r->bin_wide.p;
     a.bin_info = r->bin_info.p;
     a.bin_nbx = nbx;
@@ -714,6 +725,28 @@ int rt_export_bins(rt_renderer* r, uint32_t* headers_out, uint32_t* indices_out,
     if (wide_out && bi.wide) {
         RT_HIP(r, hipMemcpy(ent.data(), r->bin_wide.p, bi.wide * sizeof(BinEntry), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < bi.wide; ++i) wide_out[i] = ent[i].idx;
+    }
+    return RT_OK;
+}
+
+int rt_export_bin_tiles(rt_renderer* r, uint32_t* tw, uint32_t* th, uint32_t* tiles_per_bin,
+                        uint64_t* words_out) {
+    rt_bin_info bi;
+    if (const int st = rt_get_bin_info(r, &bi)) return st;
+    if (!bi.enabled) return fail(r, RT_E_STATE, "rt_export_bin_tiles: the last frame built no lists");
+    const uint32_t tpb = bin_tiles_per_bin(r->bin_tw, r->bin_th);
+    if (tw) *tw = r->bin_tw;
+    if (th) *th = r->bin_th;
+    if (tiles_per_bin) *tiles_per_bin = tpb;
+    if (words_out && bi.bins) {
+        const size_t n = size_t(bi.bins) * tpb;
+        RT_HIP(r, hipMemcpy(words_out, r->bin_hdr.p + bi.bins, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        // the builder writes the words of the bins whose lists the kernel reads
+        std::vector<uint2> hdr(bi.bins);
+        RT_HIP(r, hipMemcpy(hdr.data(), r->bin_hdr.p, bi.bins * sizeof(uint2), hipMemcpyDeviceToHost));
+        for (uint32_t b = 0; b < bi.bins; ++b)
+            if (hdr[b].y == 0u || hdr[b].y == kBinWalk)
+                for (uint32_t t = 0; t < tpb; ++t) words_out[size_t(b) * tpb + t] = 0;
     }
     return RT_OK;
 }

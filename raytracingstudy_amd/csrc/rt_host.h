@@ -66,7 +66,8 @@ struct BinBuild {
     uint32_t n_spheres;
     float K[9], R[9], o[3];     // the frame's camera (CamArgs)
     uint32_t W, H, nbx, nby;
-    double shrink;              // 1; 0.9 under the test hook RT_TEST_BIN_SHRINK
+    uint32_t tw, th;            // the frame's wave tile (WaveGrid): powers of two, <= 8
+    double shrink;             // 1; 0.9 under the test hook RT_TEST_BIN_SHRINK
     uint32_t capacity;          // entries `ent` holds
     uint32_t cap;               // a bin over it walks (<= kBinCap)
     uint32_t mean_max;          // the frame walks over this mean list length
@@ -75,9 +76,10 @@ struct BinBuild {
     uint32_t* counts;           // [nbx * nby + 1], then
     uint32_t* cursor;           // [nbx * nby] in the same allocation
     uint32_t* offs;             // [nbx * nby + 1]
-    uint2* hdr;                 // [nbx * nby]
+    uint2* hdr;                 // [nbx * nby], the tile words behind them (FrameArgs::bin_nb)
     uint4* ent;                 // [2 * capacity]
-    uint4* wide;                // [2 * kBinWideCap]
+    unsigned long long* tiles;  // [nbx * nby * tiles per bin] tile words (rt_bins_math.h)
+    uint4* wide;               // [2 * kBinWideCap]
     uint32_t* info;             // [kBinInfoWords]
     uint32_t* mirror;           // the renderer's pinned copy of info (device pointer)
     void* temp;                 // the scan's scratch
@@ -321,7 +323,11 @@ struct RendererState {
     DerivedRecords<uint32_t> bin_first_ref;
     DevBuf<uint4> bin_rects, bin_ent, bin_wide;
     DevBuf<uint32_t> bin_cnt, bin_offs, bin_info;
+    // the bins' headers, then the tile words in the same allocation: 64 per
+    // bin whatever the frame's wave tile (8 B a pixel, 16.6 MB at 1080p), so a
+    // change of spp between frames reallocates nothing
     DevBuf<uint2> bin_hdr;
+    uint32_t bin_tw = 1, bin_th = 1;  // the wave tile of the last frame that built bins
     DevBuf<unsigned char> bin_temp;
     uint32_t bin_temp_items = 0;
     uint32_t* bin_mirror = nullptr;

@@ -297,12 +297,18 @@ struct FrameArgs {
     // {first entry, count | kBinWalk} of the 8x8-pixel bin, bin_ent the
     // entries (BinEntry, two uint4 each), bin_wide the frame-level list every
     // pixel tests, bin_info[0] the frame's fallback flag (non-zero: every wave
-    // walks) and bin_info[1] the wide list's length.
+    // walks) and bin_info[1] the wide list's length.  The tile words follow
+    // the bin_nb headers in their allocation: word [bin * tiles per bin + tile]
+    // at bin_hdr + bin_nb is the wave tile's, bit k set iff the bin's entry k
+    // overlaps it (rt_bins_math.h; written for non-empty bins within the cap).
+    // (bin_nb sits in the struct's tail padding: the kernels' argument
+    // segments keep their size and the other fields their offsets.)
     const uint2* bin_hdr;
     const uint4* bin_ent;
     const uint4* bin_wide;
     const uint32_t* bin_info;
     uint32_t bin_nbx;
+    uint32_t bin_nb;
 #ifdef RT_TIMELINE
     unsigned long long* timeline;  // diagnostic build: 4 words per wave
 #endif

@@ -111,10 +111,11 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
         bool binned = false;
         if (kBin && phase == 0) {
             uint2 bh;
-            binned = !bin_header(tox, toy, bh);
-            if (binned)
-                hit = bin_nearest(bh, tox, toy, kernargs()->tw, kernargs()->th, active, r0, r1, r2, d0,
-                                  d1, d2, t, idx);
+            unsigned long long bw;
+            // (the wave tile's sides are powers of two: wave_tile_shape)
+            binned = !bin_header(tox, toy, static_cast<uint32_t>(__builtin_ctz(kernargs()->tw)),
+                                 static_cast<uint32_t>(__builtin_ctz(kernargs()->th)), bh, bw);
+            if (binned) hit = bin_nearest(bh, bw, active, r0, r1, r2, d0, d1, d2, t, idx);
         }
         if (active && !binned) {
             RT_BS(kBsPhase);

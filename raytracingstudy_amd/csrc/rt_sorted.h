@@ -145,11 +145,12 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         bool binned = false;
         if (kBin) {  // (x, y) is the wave's one pixel: a 1x1 tile of its bin
             uint2 bh;
-            binned = !bin_header(x, y, bh);
+            unsigned long long bw;
+            binned = !bin_header(x, y, 0u, 0u, bh, bw);
             if (binned) {
                 KernArgs* kc = kernargs();
-                hit = bin_nearest(bh, x, y, 1u, 1u, valid, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2], d0, d1,
-                                  d2, t, idx);
+                hit = bin_nearest(bh, bw, valid, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2], d0, d1, d2, t,
+                                  idx);
             }
         }
         if (valid && !binned) {

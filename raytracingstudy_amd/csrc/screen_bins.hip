@@ -14,8 +14,9 @@
 //                     over the buffer, wide list overflowed, lists too long on
 //                     average), mirrored into the renderer's pinned words
 //   bins_fill         per sphere: its entry into every bin it overlaps
-//   bins_sort         a wave per bin: the header, and the list sorted by
-//                     (near bound, sphere index), a lane an entry
+//   bins_sort         a wave per bin: the header, the list sorted by
+//                     (near bound, sphere index), a lane an entry, and the
+//                     bin's tile words, a lane a wave tile (round 15)
 // The order inside a list is a tracing order only: results do not depend on it.
 #include <hipcub/hipcub.hpp>
 
@@ -157,16 +158,20 @@ __global__ void __launch_bounds__(kBlockThreads)
 // A wave per bin: the header {first entry, count | kBinWalk}; a list of
 // 2 .. cap <= 64 entries is sorted ascending by (near bound, sphere index): a
 // lane holds an entry, counts the entries before it and stores its own there.
+// Then a lane owns one of the bin's tpb wave tiles (tw x th pixels) and
+// gathers its tile word (rt_bins_math.h) over the cnt entries: bit `rank` for
+// every entry whose rectangle overlaps the tile; lists of one entry too.
 __global__ void __launch_bounds__(kBlockThreads)
     bins_sort_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs, uint32_t nb,
                      uint32_t cap, const uint32_t* __restrict__ info, uint2* __restrict__ hdr,
-                     uint4* __restrict__ ent) {
+                     uint4* __restrict__ ent, uint32_t tw, uint32_t th, uint32_t tpb,
+                     unsigned long long* __restrict__ tiles) {
     const uint32_t b = blockIdx.x * (kBlockThreads / 64u) + (threadIdx.x >> 6);
     if (b >= nb) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t cnt = counts[b], off = offs[b];
     if (lane == 0u) hdr[b] = make_uint2(off, cnt > cap ? kBinWalk : cnt);
-    if (info[kBinInfoFlag] || cnt < 2u || cnt > cap || cnt > 64u) return;
+    if (info[kBinInfoFlag] || cnt < 1u || cnt > cap || cnt > 64u) return;
     uint4 a = make_uint4(0u, 0u, 0u, 0u), m = make_uint4(0u, 0u, 0u, 0u);
     if (lane < cnt) {
         a = ent[2ull * (off + lane)];
@@ -180,10 +185,18 @@ __global__ void __launch_bounds__(kBlockThreads)
         rank += o < key ? 1u : 0u;
     }
     // (every lane has read its entry: the shuffles above are after the loads)
-    if (lane < cnt) {
+    if (lane < cnt && cnt >= 2u) {
         ent[2ull * (off + rank)] = a;
         ent[2ull * (off + rank) + 1ull] = m;
     }
+    // (the keys of a list differ, each sphere enters a bin once: the ranks are 0 .. cnt - 1)
+    unsigned long long word = 0ull;
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t rc = __shfl(m.z, static_cast<int>(k), 64);
+        const uint32_t rk = __shfl(rank, static_cast<int>(k), 64);
+        if (lane < tpb && bin_rect_overlaps_tile(rc, lane, tw, th)) word |= 1ull << rk;
+    }
+    if (lane < tpb) tiles[static_cast<size_t>(b) * tpb + lane] = word;
 }
 
 }  // namespace
@@ -229,7 +242,8 @@ hipError_t launch_screen_bins(const BinBuild& b, hipStream_t st) {
         hipLaunchKernelGGL(bins_fill_kernel, dim3(ns), dim3(kBlockThreads), 0, st, b.spheres, b.first_ref,
                            b.n_spheres, b.rects, b.offs, b.cursor, b.info, b.nbx, b.capacity, b.ent);
     hipLaunchKernelGGL(bins_sort_kernel, dim3((nb + kBlockThreads / 64u - 1u) / (kBlockThreads / 64u)),
-                       dim3(kBlockThreads), 0, st, b.counts, b.offs, nb, b.cap, b.info, b.hdr, b.ent);
+                       dim3(kBlockThreads), 0, st, b.counts, b.offs, nb, b.cap, b.info, b.hdr, b.ent, b.tw,
+                       b.th, bin_tiles_per_bin(b.tw, b.th), b.tiles);
     return hipGetLastError();
 }
 

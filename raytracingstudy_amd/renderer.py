@@ -310,6 +310,18 @@ class KernelRenderer:
         check(self._lib.rt_export_bins(self._h, _vptr(hdr), _vptr(idx), _vptr(wide)), self._h)
         return hdr[:bi["bins"]], idx[:bi["entries"]], wide[:bi["wide"]]
 
+    def export_bin_tiles(self):
+        """The last frame's tile words (rt_export_bin_tiles): (tw, th) the
+        frame's wave tile in pixels and a (bins, tiles_per_bin) uint64 array,
+        bit k of a word: the bin's entry k overlaps that wave tile."""
+        bi = self.bin_info()
+        tw, th, tpb = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        check(self._lib.rt_export_bin_tiles(self._h, ctypes.byref(tw), ctypes.byref(th), ctypes.byref(tpb),
+                                            None), self._h)
+        words = np.zeros((max(bi["bins"], 1), tpb.value), np.uint64)
+        check(self._lib.rt_export_bin_tiles(self._h, None, None, None, _vptr(words)), self._h)
+        return (tw.value, th.value), words[:bi["bins"]]
+
     def scene_info(self) -> dict:
         info = RtSceneInfo()
         check(self._lib.rt_get_scene_info(self._h, ctypes.byref(info)), self._h)
