@@ -1,10 +1,12 @@
 // rt_bins_math.h — the screen-space bins' per-sphere arithmetic (DESIGN.md 5.1
-// round 10), free of HIP and of the renderer's state: plain arrays in and out,
-// f64 operations in a fixed order (built with -ffp-contract=off like the
-// rest).  screen_bins.hip runs it per sphere on the device, and
-// tests/native/bins_math_dump.cpp prints it for tests/test_bins_cpu.py on the CPU.
+// round 10) and the host's build policy, free of HIP and of the renderer's
+// state: plain arrays and integers in and out, f64 operations in a fixed order
+// (built with -ffp-contract=off like the rest).  screen_bins.hip runs the
+// arithmetic per sphere on the device, rt_bins_host.cpp the policy per frame, and
+// tests/native/bins_math_dump.cpp prints both for tests/test_bins_cpu.py on the CPU.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -183,6 +185,65 @@ RT_BINS_HD inline uint64_t bin_tile_word(const uint32_t* rects, uint32_t cnt, ui
     for (uint32_t k = 0; k < cnt && k < 64u; ++k)
         if (bin_rect_overlaps_tile(rects[k], tile, tw, th)) w |= uint64_t(1) << k;
     return w;
+}
+
+// ---- the host's policy (rt_bins_host.cpp screen_bins) ----
+// What a frame's build reports: the bin_info words on the device, mirrored to
+// the renderer's pinned copy, which the next frames read without a sync.
+enum BinInfoWord : uint32_t {
+    kBinInfoFlag = 0,   // 0: binned; kBinFlag* bits: the frame walks
+    kBinInfoWide,       // spheres in the wide list
+    kBinInfoEntries,    // total entries the frame's bins need
+    kBinInfoNonEmpty,   // bins with at least one entry
+    kBinInfoLongest,    // the longest list
+    kBinInfoOver,       // bins over the cap (their pixels walk)
+    kBinInfoFrame,      // the frame id the words belong to
+    kBinInfoWords = 8
+};
+constexpr uint32_t kBinFlagCapacity = 1u;  // the entries do not fit the buffer
+constexpr uint32_t kBinFlagWide = 2u;      // the wide list overflowed
+constexpr uint32_t kBinFlagDense = 4u;     // mean list length over kBinMeanMax
+
+// The dense-skip cadence (kBinDenseSkip) and what it is counted against.
+struct BinCadence {
+    uint32_t skip = 0;        // plain frames still to run without a build
+    uint64_t gen = 0;         // ... counted for this scene generation
+    uint32_t last_frame = 0;  // the id of the last frame that built bins (0: none, or used up below)
+};
+
+// Whether this frame builds no bins because the last build found the scene
+// too dense: it probes once in kBinDenseSkip + 1 frames.  mirror_frame /
+// mirror_flag: the pinned kBinInfoFrame / kBinInfoFlag words, which count
+// only when they belong to the last building frame.
+inline bool bin_dense_skip_step(BinCadence& c, uint64_t scene_gen, uint32_t mirror_frame,
+                                uint32_t mirror_flag) {
+    if (c.gen != scene_gen) c.skip = 0, c.gen = scene_gen;
+    if (!c.skip && c.last_frame && mirror_frame == c.last_frame && mirror_flag == kBinFlagDense) {
+        // (this frame is the first of the kBinDenseSkip skipped ones: the block below counts it)
+        c.skip = kBinDenseSkip;
+        c.last_frame = 0;  // (this observation is used up: the probe makes the next one)
+    }
+    if (!c.skip) return false;
+    --c.skip;
+    return true;
+}
+
+// The entries the bin buffer should hold (the caller allocates twice that):
+// 6 per sphere to start with (C3 needs 3.1, C5 2.0), a quarter over what the
+// last frame that built bins reported when it did not fit, never under half
+// the buffer's ent_n records now (two an entry: the buffer never shrinks),
+// never over what 32-bit entry offsets reach.
+// (capacity_test: RT_TEST_BIN_CAPACITY, a tiny first buffer, so the first frame overflows)
+inline size_t bin_entries_wanted(uint32_t capacity_test, uint32_t n_spheres, uint32_t mirror_frame,
+                                 uint32_t mirror_flag, uint32_t mirror_entries, uint32_t last_frame,
+                                 size_t ent_n) {
+    size_t want = capacity_test ? capacity_test : 6ull * n_spheres + 65536ull;
+    const size_t grown = static_cast<size_t>(mirror_entries) + mirror_entries / 4u;
+    if (last_frame && mirror_frame == last_frame && (mirror_flag & kBinFlagCapacity) && grown > want)
+        want = grown;
+    if (ent_n / 2 > want) want = ent_n / 2;
+    const size_t most = 0x7FFFFFFFull / 4u;
+    return want < most ? want : most;
 }
 
 }  // namespace rtamd

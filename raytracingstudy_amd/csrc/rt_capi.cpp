@@ -1,6 +1,7 @@
 // rt_capi.cpp — the C-ABI (include/rt.h) over the HIP kernels: handle
 // lifetime, camera state, rt_render and the display binding.  The scene is
-// rt_scene.cpp's, a frame's preparation and launch rt_frame.cpp's, the
+// rt_scene.cpp's, a frame's preparation and launch rt_frame.cpp's (its screen
+// bins rt_bins_host.cpp's), the queries and the G-buffer rt_queries.cpp's, the
 // multi-device handle rt_multi.cpp's; rt_host.h holds what they share.
 //
 // Host runtime that replaces KernelRenderer (include/renderer.cuh:25-50,
@@ -190,14 +191,14 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
     // radii x 0.9 (a negative control: unsound lists), the frame size below
     // which a frame walks
     if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_CAP"))
-        r->bin_cap = static_cast<uint32_t>(std::min<unsigned long>(64ul, strtoul(v, nullptr, 10)));
+        r->bins.cap = static_cast<uint32_t>(std::min<unsigned long>(64ul, strtoul(v, nullptr, 10)));
     if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_CAPACITY"))
-        r->bin_capacity_test = static_cast<uint32_t>(std::max(1ul, std::min(1ul << 24, strtoul(v, nullptr, 10))));
-    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_SHRINK")) r->bin_shrink = atoi(v) != 0 ? 0.9 : 1.0;
-    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_MIN_SAMPLES")) r->bin_min_samples = strtoull(v, nullptr, 10);
+        r->bins.capacity_test = static_cast<uint32_t>(std::max(1ul, std::min(1ul << 24, strtoul(v, nullptr, 10))));
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_SHRINK")) r->bins.shrink = atoi(v) != 0 ? 0.9 : 1.0;
+    if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_MIN_SAMPLES")) r->bins.min_samples = strtoull(v, nullptr, 10);
     // ... and the mean list length over which a frame walks (tiny test frames are dense)
     if (const char* v = test_env(cfg->flags, "RT_TEST_BIN_MEAN"))
-        r->bin_mean_max = static_cast<uint32_t>(std::min(1ul << 20, strtoul(v, nullptr, 10)));
+        r->bins.mean_max = static_cast<uint32_t>(std::min(1ul << 20, strtoul(v, nullptr, 10)));
     if (const char* fe = test_env(cfg->flags, "RT_TEST_FAULT"))
         r->test_fault_queue = strcmp(fe, "queue:0") == 0;
     // ... and the A/B switches ("0" off, any other number on)
@@ -227,14 +228,14 @@ int rt_create(const rt_config* cfg, rt_renderer** out) {
         e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->qerr_dev), r->qerr_host, 0);
     }
     // the screen-space bins' info words: pinned like the failure word
-    if (e == hipSuccess) e = hipEventCreate(&r->bin_e0);
-    if (e == hipSuccess) e = hipEventCreate(&r->bin_e1);
+    if (e == hipSuccess) e = hipEventCreate(&r->bins.e0);
+    if (e == hipSuccess) e = hipEventCreate(&r->bins.e1);
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void**>(&r->bin_mirror), kBinInfoWords * sizeof(uint32_t),
+        e = hipHostMalloc(reinterpret_cast<void**>(&r->bins.mirror), kBinInfoWords * sizeof(uint32_t),
                           hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) {
-        memset(r->bin_mirror, 0, kBinInfoWords * sizeof(uint32_t));
-        e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->bin_mirror_dev), r->bin_mirror, 0);
+        memset(r->bins.mirror, 0, kBinInfoWords * sizeof(uint32_t));
+        e = hipHostGetDevicePointer(reinterpret_cast<void**>(&r->bins.mirror_dev), r->bins.mirror, 0);
     }
     if (e != hipSuccess) {
         st = hip_fail(nullptr, e, "rt_create");
@@ -274,30 +275,12 @@ int rt_destroy(rt_renderer* r) {
     r->prim_cam8.buf.release();
     r->prim_shd8.buf.release();
     r->d_shd_rr.release();
-    r->q_counters.release();
-    r->q_ray.release();
-    r->q_hit.release();
-    r->q_multi_hits.release();
-    r->q_multi_count.release();
-    r->q_probe.release();
-    r->q_overlap_idx.release();
-    r->q_overlap_count.release();
+    r->q.release();
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();
     r->occ.release();
-    r->bin_first_ref.buf.release();
-    r->bin_rects.release();
-    r->bin_ent.release();
-    r->bin_wide.release();
-    r->bin_cnt.release();
-    r->bin_offs.release();
-    r->bin_info.release();
-    r->bin_hdr.release();
-    r->bin_temp.release();
-    if (r->bin_e0) (void)hipEventDestroy(r->bin_e0);
-    if (r->bin_e1) (void)hipEventDestroy(r->bin_e1);
-    if (r->bin_mirror) (void)hipHostFree(r->bin_mirror);
+    r->bins.release();  // (its buffers, events and pinned words)
     if (r->occ_e0) (void)hipEventDestroy(r->occ_e0);
     if (r->occ_e1) (void)hipEventDestroy(r->occ_e1);
     if (r->ev0) (void)hipEventDestroy(r->ev0);

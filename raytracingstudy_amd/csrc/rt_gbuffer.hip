@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_params.h"
+#include "rt_query_common.h"
+#include "rt_shade.h"  // get_ray: Camera::getRay as rt_pick and the frames' unjittered sample cast it
 #include "rt_walk.h"
 
 namespace rtamd {
@@ -23,35 +25,13 @@ struct GBufferArgs {
     unsigned long long* counters; // stats launches: 8 lines of kStatLineStride words
 };
 
-// include/camera.h:24-41 — Camera::getRay, restated from rt_kernels.hip so that
-// file stays as it is: the same operations in the same order, hence the bits
-// rt_pick and the frames' unjittered sample cast.
-__device__ __forceinline__ void gbuffer_get_ray(const CamArgs& c, float u, float v, float& wx,
-                                                float& wy, float& wz) {
-    const float dx = (u - c.K[2]) / c.K[0];
-    const float dy = (v - c.K[5]) / c.K[4];
-    const float dz = 1.0f;
-    wx = c.R[0] * dx + c.R[3] * dy + c.R[6] * dz;
-    wy = c.R[1] * dx + c.R[4] * dy + c.R[7] * dz;
-    wz = c.R[2] * dx + c.R[5] * dy + c.R[8] * dz;
-    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
-    wx /= len;
-    wy /= len;
-    wz /= len;
-}
-
-__device__ __forceinline__ unsigned long long gbuffer_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // A 256-thread block is a 16x16 pixel tile, each of its 4 waves an 8x8 quarter
 // (lane = 8 * row + column): a wave's 64 rays are neighbours, and a wave's
 // stores are 8 row segments of 64 B (hits), 128 B (normals) and 32 B (albedo).
 // FrameArgs leads the argument block (the kernargs() rule of DESIGN.md 5.7):
 // a.cam, a.sc, a.W and a.H are set, the rest is zero.  The dynamic LDS is the
 // per-lane ancestor stack alone: [level][thread], stack_levels(a.sc) levels.
+// (rt_query_common.h holds what is shared; the stack and the flush stay here: a helper moves registers in the stats instances)
 template <bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) gbuffer_kernel(FrameArgs a, GBufferArgs g) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -62,7 +42,7 @@ __global__ void __launch_bounds__(kBlockThreads) gbuffer_kernel(FrameArgs a, GBu
     uint32_t n_nodes = 0, n_prims = 0;
     if (x < a.W && y < a.H) {
         float d0, d1, d2;
-        gbuffer_get_ray(a.cam, static_cast<float>(x), static_cast<float>(y), d0, d1, d2);
+        get_ray(a.cam, static_cast<float>(x), static_cast<float>(y), d0, d1, d2);
         float t = __builtin_inff();  // a miss reports tmax
         uint32_t ref = kNoHit;
         const bool hit = walk<GenericRay<false, kStats>>(
@@ -91,8 +71,8 @@ __global__ void __launch_bounds__(kBlockThreads) gbuffer_kernel(FrameArgs a, GBu
     if (kStats) {
         // per wave, one 128-byte line per XCD group (query_kernel's layout:
         // words 2 and 3 of a line; the ray count is the host's W * H)
-        const unsigned long long s2 = gbuffer_wave_sum(n_nodes);
-        const unsigned long long s3 = gbuffer_wave_sum(n_prims);
+        const unsigned long long s2 = query_wave_sum(n_nodes);
+        const unsigned long long s3 = query_wave_sum(n_prims);
         if (lane == 0) {
             const uint32_t b = blockIdx.y * gridDim.x + blockIdx.x;
             unsigned long long* c = g.counters + (b & 7u) * kStatLineStride;
@@ -114,7 +94,7 @@ hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* a
     g.counters = counters;
     const dim3 grid((a.W + kTileSide - 1u) / kTileSide, (a.H + kTileSide - 1u) / kTileSide);
     const dim3 block(kBlockThreads);
-    const size_t lds = static_cast<size_t>(stack_levels(a.sc)) * kBlockThreads * sizeof(uint2);
+    const size_t lds = query_stack_bytes(stack_levels(a.sc));
     if (counters) hipLaunchKernelGGL((gbuffer_kernel<true>), grid, block, lds, st, a, g);
     else hipLaunchKernelGGL((gbuffer_kernel<false>), grid, block, lds, st, a, g);
     return hipGetLastError();

@@ -3,7 +3,9 @@
 // stream-ordering helpers, and the functions the units call across.
 //   rt_capi.cpp   handle lifetime, camera, rt_render and the display binding
 //   rt_scene.cpp  scene upload, octree build, exports
-//   rt_frame.cpp  per-frame preparation and launch, tiles, queries, G-buffer
+//   rt_frame.cpp  per-frame preparation and launch (do_render's steps), tiles
+//   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
+//   rt_queries.cpp    ray, multi-hit and overlap queries, picking, the G-buffer
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -202,6 +204,72 @@ struct MultiState {
     uint32_t* d_all_ids = nullptr;         // on devices[0]
 };
 
+// The screen-space bins of a renderer (screen_bins.hip, DESIGN.md 5.1 round
+// 10), rebuilt by every plain frame that reads them (rt_bins_host.cpp).
+struct ScreenBinState {
+    DerivedRecords<uint32_t> first_ref;  // per sphere, made once per scene
+    DevBuf<uint4> rects, ent, wide;
+    DevBuf<uint32_t> cnt, offs, info;    // cnt: counts and cursors; info: the frame's info words
+    // the bins' headers, then the tile words in the same allocation: 64 per
+    // bin whatever the frame's wave tile (8 B a pixel, 16.6 MB at 1080p), so a
+    // change of spp between frames reallocates nothing
+    DevBuf<uint2> hdr;
+    uint32_t tw = 1, th = 1;  // the wave tile of the last frame that built bins
+    DevBuf<unsigned char> temp;
+    uint32_t temp_items = 0;
+    // the pinned host copy of the info words, which the next rt_render reads
+    // without a sync (a frame that overflowed `ent` walks, and the next frame
+    // gets a larger buffer), and its device pointer
+    uint32_t* mirror = nullptr;
+    uint32_t* mirror_dev = nullptr;
+    // the RT_TEST_BIN_* hooks: cap, capacity_test, shrink, min_samples, mean_max (kBinMeanMax)
+    uint32_t cap = 64, capacity_test = 0, mean_max = 48;
+    double shrink = 1.0;
+    uint64_t min_samples = kBinMinSamples;
+    BinCadence cadence;                        // the dense skip; the last building frame's id
+    uint32_t last_reason = RT_BINS_NO_FRAME;  // why the last frame had bins or not (rt_get_bin_info)
+    uint32_t last_capacity = 0, nbx = 0, nby = 0;  // ... and that build's sizes
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool timing = false, timed = false;
+    void release() {
+        first_ref.buf.release();
+        rects.release();
+        ent.release();
+        wide.release();
+        cnt.release();
+        offs.release();
+        info.release();
+        hdr.release();
+        temp.release();
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (mirror) (void)hipHostFree(mirror);
+    }
+};
+
+// The query path's scratch (rt_queries.cpp): its own stat lines (a query never
+// touches the frames' counter sets) and the single-item wrappers' records.
+struct QueryScratch {
+    DevBuf<unsigned long long> counters;
+    DevBuf<float4> ray;              // rt_pick, rt_pick_multi: one ray
+    DevBuf<uint2> hit;               // rt_pick: one hit
+    DevBuf<uint2> multi_hits;        // rt_pick_multi: up to RT_MULTIHIT_MAX hits
+    DevBuf<uint32_t> multi_count;    // ... and the count
+    DevBuf<float4> probe;            // rt_overlaps_at: the probe,
+    DevBuf<uint32_t> overlap_idx;    // up to RT_OVERLAP_MAX indices
+    DevBuf<uint32_t> overlap_count;  // and the count word
+    void release() {
+        counters.release();
+        ray.release();
+        hit.release();
+        multi_hits.release();
+        multi_count.release();
+        probe.release();
+        overlap_idx.release();
+        overlap_count.release();
+    }
+};
+
 // what an rt_renderer holds (the C-ABI's opaque struct, below, is exactly this)
 struct RendererState {
     rt_config cfg;
@@ -313,48 +381,8 @@ struct RendererState {
     hipEvent_t occ_e0 = nullptr, occ_e1 = nullptr;
     bool occ_timed = false;
     double occ_M = 0.0;
-    // screen-space bins (screen_bins.hip), rebuilt by
-    // every plain frame that reads them.  bin_first_ref: per sphere, made once
-    // per scene.  bin_cnt: counts and cursors; bin_info / bin_mirror: the
-    // frame's info words on the device and their pinned host copy, which the
-    // next rt_render reads without a sync (a frame that overflowed bin_ent
-    // walks, and the next frame gets a larger buffer).  bin_cap /
-    // bin_capacity_test / bin_shrink / bin_min_samples / bin_mean_max: RT_TEST_BIN_* hooks.
-    DerivedRecords<uint32_t> bin_first_ref;
-    DevBuf<uint4> bin_rects, bin_ent, bin_wide;
-    DevBuf<uint32_t> bin_cnt, bin_offs, bin_info;
-    // the bins' headers, then the tile words in the same allocation: 64 per
-    // bin whatever the frame's wave tile (8 B a pixel, 16.6 MB at 1080p), so a
-    // change of spp between frames reallocates nothing
-    DevBuf<uint2> bin_hdr;
-    uint32_t bin_tw = 1, bin_th = 1;  // the wave tile of the last frame that built bins
-    DevBuf<unsigned char> bin_temp;
-    uint32_t bin_temp_items = 0;
-    uint32_t* bin_mirror = nullptr;
-    uint32_t* bin_mirror_dev = nullptr;
-    uint32_t bin_cap = 64, bin_capacity_test = 0, bin_nbx = 0, bin_nby = 0;
-    double bin_shrink = 1.0;
-    uint64_t bin_min_samples = kBinMinSamples;
-    uint32_t bin_dense_skip = 0;    // plain frames still to run without a build (kBinDenseSkip)
-    uint64_t bin_skip_gen = 0;      // ... counted for this scene generation
-    uint32_t bin_mean_max = 48;     // kBinMeanMax (RT_TEST_BIN_MEAN)
-    uint32_t bin_last_reason = RT_BINS_NO_FRAME;   // RT_BINS_NO_FRAME
-    uint32_t bin_last_frame = 0;    // the frame id of the last frame that built bins
-    uint32_t bin_last_capacity = 0;
-    hipEvent_t bin_e0 = nullptr, bin_e1 = nullptr;
-    bool bin_timing = false, bin_timed = false;
-    // ray queries (rt_trace_rays, rt_pick): their own stat lines (a query never
-    // touches the frames' counter sets) and rt_pick's one ray and one hit
-    DevBuf<unsigned long long> q_counters;
-    DevBuf<float4> q_ray;
-    DevBuf<uint2> q_hit;
-    // rt_pick_multi's hits (up to RT_MULTIHIT_MAX) and its count
-    DevBuf<uint2> q_multi_hits;
-    DevBuf<uint32_t> q_multi_count;
-    // rt_overlaps_at's probe, its indices (up to RT_OVERLAP_MAX) and its count word
-    DevBuf<float4> q_probe;
-    DevBuf<uint32_t> q_overlap_idx;
-    DevBuf<uint32_t> q_overlap_count;
+    ScreenBinState bins;
+    QueryScratch q;
     rt_scene_info info{};
     std::string err;
     // multi-device handle (rt_create_multi): this renderer is devices[0]'s
@@ -392,6 +420,16 @@ int render_tiles_one(rt_renderer* r, const uint32_t* tile_ids, uint32_t n_tiles,
                      void* dev_packed, void* stream, rt_stats* stats);
 int unpack_tiles_one(rt_renderer* r, const void* dev_packed, const uint32_t* tile_ids,
                      uint32_t n_tiles, uint32_t ts, void* dev_rgba8, void* stream);
+// the work counters of a stats launch: {primary, shadow, nodes, prims} per XCD
+// group, one line each (kStatLineBase), summed into c
+constexpr size_t kStatLineWords = 8 * kStatLineStride;
+inline void sum_stat_lines(const unsigned long long* lines, unsigned long long c[4]) {
+    for (uint32_t i = 0; i < 4; ++i) c[i] = 0;
+    for (uint32_t q = 0; q < 8; ++q)
+        for (uint32_t i = 0; i < 4; ++i) c[i] += lines[q * kStatLineStride + i];
+}
+// rt_bins_host.cpp: do_render's step 4b
+int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st);
 // rt_multi.cpp: a multi-device handle's part of the calls above
 int multi_render(rt_renderer* r, uint32_t* out, hipStream_t hs, rt_stats* stats);
 int multi_wait(rt_renderer* r);

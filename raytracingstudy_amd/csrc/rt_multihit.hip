@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_params.h"
+#include "rt_query_common.h"
 #include "rt_walk.h"
 
 namespace rtamd {
@@ -23,12 +24,6 @@ struct MultiQueryArgs {
     unsigned long long* counters;  // stats launches: 8 lines of kStatLineStride words
 };
 
-__device__ __forceinline__ unsigned long long multi_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // One ray per lane, 256-thread blocks, the K-entry buffer in registers (K is
 // the caller's k rounded up to a compiled size: the walk keeps the K nearest
 // and the lane writes the first k of them, so slots, fillers and counts are
@@ -36,6 +31,7 @@ __device__ __forceinline__ unsigned long long multi_wave_sum(unsigned long long 
 // stores.  FrameArgs leads the argument block for rt_query.hip's reason:
 // kernargs() reinterprets the argument segment as FrameArgs.  The dynamic LDS
 // is the per-lane ancestor stack alone, [level][thread].
+// (rt_query_common.h holds what is shared; the stack and the flush stay here: a helper moves registers in the stats instances)
 template <int K, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) multihit_kernel(FrameArgs a, MultiQueryArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -68,20 +64,14 @@ __global__ void __launch_bounds__(kBlockThreads) multihit_kernel(FrameArgs a, Mu
     }
     if (kStats) {
         // rt_query.hip's layout: words 2 and 3 of one line per XCD group
-        const unsigned long long s2 = multi_wave_sum(n_nodes);
-        const unsigned long long s3 = multi_wave_sum(n_prims);
+        const unsigned long long s2 = query_wave_sum(n_nodes);
+        const unsigned long long s3 = query_wave_sum(n_prims);
         if ((threadIdx.x & 63u) == 0) {
             unsigned long long* c = q.counters + (blockIdx.x & 7u) * kStatLineStride;
             atomicAdd(c + 2, s2);
             atomicAdd(c + 3, s3);
         }
     }
-}
-
-template <int K>
-static void launch_k(const FrameArgs& a, const MultiQueryArgs& q, dim3 grid, size_t lds, hipStream_t st) {
-    if (q.counters) hipLaunchKernelGGL((multihit_kernel<K, true>), grid, dim3(kBlockThreads), lds, st, a, q);
-    else hipLaunchKernelGGL((multihit_kernel<K, false>), grid, dim3(kBlockThreads), lds, st, a, q);
 }
 
 // a.sc is the scene; the rest of `a` is unused by the kernel (see above).
@@ -98,14 +88,13 @@ hipError_t launch_multihit(const FrameArgs& a, const void* rays, void* hits, voi
     q.n = n;
     q.k = k;
     q.counters = counters;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlockThreads - 1u) / kBlockThreads));
-    const size_t lds = static_cast<size_t>(stack_levels(a.sc)) * kBlockThreads * sizeof(uint2);
+    const dim3 grid = query_grid(n), block(kBlockThreads);
+    const size_t lds = query_stack_bytes(stack_levels(a.sc));
     // compiled sizes 1, 2, 4, 8, 16: k = 1 runs the nearest walk's own stop rule
-    if (k == 1) launch_k<1>(a, q, grid, lds, st);
-    else if (k == 2) launch_k<2>(a, q, grid, lds, st);
-    else if (k <= 4) launch_k<4>(a, q, grid, lds, st);
-    else if (k <= 8) launch_k<8>(a, q, grid, lds, st);
-    else launch_k<16>(a, q, grid, lds, st);
+    launch_for_k(k, [&](auto K) {
+        if (counters) hipLaunchKernelGGL((multihit_kernel<K(), true>), grid, block, lds, st, a, q);
+        else hipLaunchKernelGGL((multihit_kernel<K(), false>), grid, block, lds, st, a, q);
+    });
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@
 
 #include "rt_overlap_math.h"
 #include "rt_params.h"
+#include "rt_query_common.h"
 #include "rt_walk.h"
 
 namespace rtamd {
@@ -28,12 +29,6 @@ struct OverlapArgs {
 };
 
 constexpr uint32_t kOverlapMore = 0x80000000u;  // RT_OVERLAP_MORE
-
-__device__ __forceinline__ unsigned long long overlap_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // One lane's K smallest accepted sphere indices, ascending, a free slot
 // kNoHit (which sorts after every index).  `more`: a sphere that is not held
@@ -93,6 +88,7 @@ __device__ __forceinline__ uint32_t children_met(const OverlapBox& b, uint32_t l
 // dynamic LDS is the per-lane descent stack, [level][thread]: level d holds
 // the node at depth d while the lane is below it: {first child slot, valid |
 // leaf << 8 | children still to visit << 16}.
+// (rt_query_common.h holds what is shared; the stack and the flush stay here: a helper moves registers in the stats instances)
 template <int K, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, OverlapArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -191,20 +187,14 @@ __global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, Ove
     }
     if (kStats) {
         // rt_query.hip's layout: words 2 and 3 of one line per XCD group
-        const unsigned long long s2 = overlap_wave_sum(n_nodes);
-        const unsigned long long s3 = overlap_wave_sum(n_prims);
+        const unsigned long long s2 = query_wave_sum(n_nodes);
+        const unsigned long long s3 = query_wave_sum(n_prims);
         if ((threadIdx.x & 63u) == 0) {
             unsigned long long* c = q.counters + (blockIdx.x & 7u) * kStatLineStride;
             atomicAdd(c + 2, s2);
             atomicAdd(c + 3, s3);
         }
     }
-}
-
-template <int K>
-static void launch_k(const FrameArgs& a, const OverlapArgs& q, dim3 grid, size_t lds, hipStream_t st) {
-    if (q.counters) hipLaunchKernelGGL((overlap_kernel<K, true>), grid, dim3(kBlockThreads), lds, st, a, q);
-    else hipLaunchKernelGGL((overlap_kernel<K, false>), grid, dim3(kBlockThreads), lds, st, a, q);
 }
 
 // a.sc is the scene; the rest of `a` is unused by the kernel.  1 <= k <= 16
@@ -229,13 +219,12 @@ hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices,
     q.levels = a.sc.stack_depth ? a.sc.stack_depth : 1u;
     q.slack_m = slack_m;
     q.counters = counters;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlockThreads - 1u) / kBlockThreads));
-    const size_t lds = static_cast<size_t>(q.levels) * kBlockThreads * sizeof(uint2);
-    if (k == 1) launch_k<1>(a, q, grid, lds, st);
-    else if (k == 2) launch_k<2>(a, q, grid, lds, st);
-    else if (k <= 4) launch_k<4>(a, q, grid, lds, st);
-    else if (k <= 8) launch_k<8>(a, q, grid, lds, st);
-    else launch_k<16>(a, q, grid, lds, st);
+    const dim3 grid = query_grid(n), block(kBlockThreads);
+    const size_t lds = query_stack_bytes(q.levels);
+    launch_for_k(k, [&](auto K) {
+        if (counters) hipLaunchKernelGGL((overlap_kernel<K(), true>), grid, block, lds, st, a, q);
+        else hipLaunchKernelGGL((overlap_kernel<K(), false>), grid, block, lds, st, a, q);
+    });
     return hipGetLastError();
 }
 

@@ -211,20 +211,7 @@ struct BinEntry {
     float near_t;
 };
 static_assert(sizeof(BinEntry) == 32, "two uint4 per entry");
-// bin_info words (device, mirrored to the renderer's pinned copy)
-enum BinInfoWord : uint32_t {
-    kBinInfoFlag = 0,   // 0: binned; kBinFlag* bits: the frame walks
-    kBinInfoWide,       // spheres in the wide list
-    kBinInfoEntries,    // total entries the frame's bins need
-    kBinInfoNonEmpty,   // bins with at least one entry
-    kBinInfoLongest,    // the longest list
-    kBinInfoOver,       // bins over the cap (their pixels walk)
-    kBinInfoFrame,      // the frame id the words belong to
-    kBinInfoWords = 8
-};
-constexpr uint32_t kBinFlagCapacity = 1u;  // the entries do not fit the buffer
-constexpr uint32_t kBinFlagWide = 2u;      // the wide list overflowed
-constexpr uint32_t kBinFlagDense = 4u;     // mean list length over kBinMeanMax
+// (the bin_info words and their flag bits: rt_bins_math.h, beside the host policy that reads them)
 
 // Slack of the camera-relative screen, in units of 2^-24: the
 // screen may only pass MORE spheres than the exact test, so C' undercuts

@@ -1,0 +1,278 @@
+// rt_queries.cpp — the calls that read a scene without rendering a frame
+// (DESIGN.md 5.7): ray, multi-hit and sphere-overlap queries, their
+// single-item wrappers, the first-hit G-buffer.  The reference has none
+// (Octree::traverse is a stub, include/octree.h:19-21; its render kernel
+// writes one colour per pixel, src/renderer.cu:57-82).  A query reads scene
+// (the G-buffer: and camera) state only: it takes no frame id, leaves the
+// progressive sums, the frames' counter sets and the qerr word alone, and is
+// ordered after the handle's earlier work like every launch.  Each entry point
+// checks its own arguments in its own order (rt.h states the codes); what
+// follows the checks is stated once, in query_begin and query_launch.
+#include "rt_host.h"
+
+using namespace rtamd;
+
+namespace {
+
+// The device, the stream (the caller's, or the handle's own), the ordering
+// after the handle's last work, and the kernels' leading argument: a FrameArgs
+// (kernargs() reinterprets the argument segment as one, rt_query.hip) holding
+// the scene, the rest zero.
+int query_begin(rt_renderer* r, void* stream, hipStream_t& hs, FrameArgs& a) {
+    int st;
+    if ((st = set_device(r))) return st;
+    hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    memset(&a, 0, sizeof(a));
+    a.sc = r->sc;
+    return RT_OK;
+}
+
+// The query path's own stat lines (a stats launch never touches the frames'
+// counter sets): zeroed on `hs` with the start event behind them; after the
+// launch and the end event, read back into `stats` (nodes, tests and ms).
+int query_stats_begin(rt_renderer* r, hipStream_t hs, unsigned long long*& ctr) {
+    int st;
+    if ((st = ensure(r, r->q.counters, kStatLineWords))) return st;
+    ctr = r->q.counters.p;
+    RT_HIP(r, hipMemsetAsync(ctr, 0, kStatLineWords * sizeof(unsigned long long), hs));
+    RT_HIP(r, hipEventRecord(r->ev0, hs));
+    return RT_OK;
+}
+int query_stats_read(rt_renderer* r, const unsigned long long* ctr, rt_stats* stats) {
+    RT_HIP(r, hipEventSynchronize(r->ev1));
+    unsigned long long lines[kStatLineWords], c[4];
+    RT_HIP(r, hipMemcpy(lines, ctr, sizeof(lines), hipMemcpyDeviceToHost));
+    sum_stat_lines(lines, c);
+    float ms = 0.f;
+    RT_HIP(r, hipEventElapsedTime(&ms, r->ev0, r->ev1));
+    memset(stats, 0, sizeof(*stats));
+    stats->nodes_visited = c[2];
+    stats->prims_tested = c[3];
+    stats->ms = ms;
+    return RT_OK;
+}
+
+// launch(ctr) on `hs`, ctr the stat lines of a stats launch or null: between
+// the stats bracket when `stats` is given, and marked as the handle's last
+// work.  The caller adds its ray count to `stats`.
+template <typename Launch>
+int query_launch(rt_renderer* r, const char* api, hipStream_t hs, rt_stats* stats, Launch launch) {
+    int st;
+    unsigned long long* ctr = nullptr;
+    if (stats && (st = query_stats_begin(r, hs, ctr))) return st;
+    hipError_t e = launch(ctr);
+    if (e != hipSuccess) return hip_fail(r, e, (std::string(api) + ": kernel launch").c_str());
+    if (stats) RT_HIP(r, hipEventRecord(r->ev1, hs));
+    if ((st = mark_queued(r, hs))) return st;
+    return stats ? query_stats_read(r, ctr, stats) : RT_OK;
+}
+
+// n == 0: nothing to do, and a stats call reports nothing done
+int nothing_queried(rt_stats* stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return RT_OK;
+}
+
+// rt_pick's ray through image coordinates (u, v): tmin = 0, tmax = +inf.
+void pick_ray(const rt_renderer* r, float u, float v, float4 ray[2]) {
+    // Camera::getRay (include/camera.h:24-41) in source order on the host (built
+    // with -ffp-contract=off, IEEE division and sqrt): the same bits as the CPU oracle's getRay
+    const float* K = r->K;
+    const float* P = r->pose;
+    const float dx = (u - K[2]) / K[0];
+    const float dy = (v - K[5]) / K[4];
+    const float dz = 1.0f;
+    float wx = P[0] * dx + P[4] * dy + P[8] * dz;
+    float wy = P[1] * dx + P[5] * dy + P[9] * dz;
+    float wz = P[2] * dx + P[6] * dy + P[10] * dz;
+    const float len = sqrtf(wx * wx + wy * wy + wz * wz);
+    wx /= len;
+    wy /= len;
+    wz /= len;
+    ray[0] = make_float4(P[12], P[13], P[14], 0.0f);
+    ray[1] = make_float4(wx, wy, wz, INFINITY);
+}
+
+}  // namespace
+
+// The three single-item wrappers below (rt_pick, rt_pick_multi, rt_overlaps_at)
+// stay plain functions: their scratch buffers and copies back differ in
+// number and type, so a shared helper could hold only "order, upload one
+// record" (three lines of each), would need the rest passed in as two
+// callbacks, and would be no shorter than what it replaces.
+extern "C" {
+
+int rt_trace_rays(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t kind, void* dev_hits,
+                  void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_trace_rays: null handle");
+    if (kind != RT_QUERY_NEAREST && kind != RT_QUERY_ANY)
+        return fail(r, RT_E_INVALID, "rt_trace_rays: unknown query kind");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_trace_rays: no scene (rt_set_scene first)");
+    if (n == 0) return nothing_queried(stats);
+    if (!dev_rays || !dev_hits) return fail(r, RT_E_INVALID, "rt_trace_rays: null buffer");
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    st = query_launch(r, "rt_trace_rays", hs, stats, [&](unsigned long long* ctr) {
+        return launch_query(a, dev_rays, dev_hits, n, kind == RT_QUERY_ANY, ctr, hs);
+    });
+    if (!st && stats) (kind == RT_QUERY_ANY ? stats->shadow_rays : stats->primary_rays) = n;
+    return st;
+}
+
+int rt_pick(rt_renderer* r, float u, float v, rt_hit* hit_out, float point_out[3]) {
+    if (!r || !hit_out) return fail(r, RT_E_INVALID, "rt_pick: null argument");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick: no scene (rt_set_scene first)");
+    float4 ray[2];
+    pick_ray(r, u, v, ray);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q.ray, 2)) || (st = ensure(r, r->q.hit, 1))) return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q.ray.p, ray, sizeof(ray), hipMemcpyHostToDevice, hs));
+    if ((st = rt_trace_rays(r, r->q.ray.p, 1, RT_QUERY_NEAREST, r->q.hit.p, hs, nullptr))) return st;
+    uint2 h;
+    RT_HIP(r, hipMemcpyAsync(&h, r->q.hit.p, sizeof(h), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    memcpy(&hit_out->t, &h.x, sizeof(float));
+    hit_out->sphere = h.y;
+    if (point_out) {
+        const float o[3] = {ray[0].x, ray[0].y, ray[0].z}, d[3] = {ray[1].x, ray[1].y, ray[1].z};
+        for (int i = 0; i < 3; ++i) point_out[i] = o[i] + hit_out->t * d[i];
+    }
+    return RT_OK;
+}
+
+// Ordered multi-hit queries: the k nearest spheres of each ray
+// by (t, sphere index).
+int rt_trace_rays_multi(rt_renderer* r, const void* dev_rays, uint32_t n, uint32_t k, void* dev_hits,
+                        void* dev_counts, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_trace_rays_multi: null handle");
+    if (k == 0 || k > RT_MULTIHIT_MAX)
+        return fail(r, RT_E_INVALID, "rt_trace_rays_multi: k must be 1 .. RT_MULTIHIT_MAX");
+    if (!r->has_scene)
+        return fail(r, RT_E_NOSCENE, "rt_trace_rays_multi: no scene (rt_set_scene first)");
+    if (n == 0) return nothing_queried(stats);
+    if (!dev_rays || !dev_hits) return fail(r, RT_E_INVALID, "rt_trace_rays_multi: null buffer");
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    st = query_launch(r, "rt_trace_rays_multi", hs, stats, [&](unsigned long long* ctr) {
+        return launch_multihit(a, dev_rays, dev_hits, dev_counts, n, k, ctr, hs);
+    });
+    if (!st && stats) stats->primary_rays = n;
+    return st;
+}
+
+int rt_pick_multi(rt_renderer* r, float u, float v, uint32_t k, rt_hit* hits_out, uint32_t* count_out) {
+    if (!r || !hits_out) return fail(r, RT_E_INVALID, "rt_pick_multi: null argument");
+    if (k == 0 || k > RT_MULTIHIT_MAX)
+        return fail(r, RT_E_INVALID, "rt_pick_multi: k must be 1 .. RT_MULTIHIT_MAX");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick_multi: no scene (rt_set_scene first)");
+    float4 ray[2];
+    pick_ray(r, u, v, ray);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q.ray, 2)) || (st = ensure(r, r->q.multi_hits, RT_MULTIHIT_MAX)) ||
+        (st = ensure(r, r->q.multi_count, 1)))
+        return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q.ray.p, ray, sizeof(ray), hipMemcpyHostToDevice, hs));
+    if ((st = rt_trace_rays_multi(r, r->q.ray.p, 1, k, r->q.multi_hits.p, r->q.multi_count.p, hs, nullptr)))
+        return st;
+    uint2 h[RT_MULTIHIT_MAX];
+    uint32_t count = 0;
+    RT_HIP(r, hipMemcpyAsync(h, r->q.multi_hits.p, k * sizeof(uint2), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipMemcpyAsync(&count, r->q.multi_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    for (uint32_t s = 0; s < k; ++s) {
+        memcpy(&hits_out[s].t, &h[s].x, sizeof(float));
+        hits_out[s].sphere = h[s].y;
+    }
+    if (count_out) *count_out = count;
+    return RT_OK;
+}
+
+// Sphere-overlap queries: the scene spheres each probe sphere
+// touches, the k smallest indices.
+int rt_query_overlaps(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_t k, uint32_t flags,
+                      void* dev_indices, void* dev_counts, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_query_overlaps: null handle");
+    if (k == 0 || k > RT_OVERLAP_MAX)
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: k must be 1 .. RT_OVERLAP_MAX");
+    if (flags & ~static_cast<uint32_t>(RT_OVERLAP_SKIP_SELF))
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: unknown flag bits");
+    if (n > 0 && (!dev_probes || !dev_indices))
+        return fail(r, RT_E_INVALID, "rt_query_overlaps: null buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_query_overlaps: no scene (rt_set_scene first)");
+    if (n == 0) return nothing_queried(stats);
+    hipStream_t hs;
+    FrameArgs a;
+    if (const int st = query_begin(r, stream, hs, a)) return st;
+    const float slack_m = overlap_slack_m(r->info.root_min, r->info.root_max);
+    // (no rays: both ray counts stay 0)
+    return query_launch(r, "rt_query_overlaps", hs, stats, [&](unsigned long long* ctr) {
+        return launch_overlap(a, dev_probes, dev_indices, dev_counts, n, k,
+                              (flags & RT_OVERLAP_SKIP_SELF) != 0, slack_m, ctr, hs);
+    });
+}
+
+int rt_overlaps_at(rt_renderer* r, const float center[3], float radius, uint32_t k,
+                   uint32_t* indices_out, uint32_t* count_out) {
+    if (!r || !center || !indices_out) return fail(r, RT_E_INVALID, "rt_overlaps_at: null argument");
+    if (k == 0 || k > RT_OVERLAP_MAX)
+        return fail(r, RT_E_INVALID, "rt_overlaps_at: k must be 1 .. RT_OVERLAP_MAX");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_overlaps_at: no scene (rt_set_scene first)");
+    const float4 probe = make_float4(center[0], center[1], center[2], radius);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q.probe, 1)) || (st = ensure(r, r->q.overlap_idx, RT_OVERLAP_MAX)) ||
+        (st = ensure(r, r->q.overlap_count, 1)))
+        return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q.probe.p, &probe, sizeof(probe), hipMemcpyHostToDevice, hs));
+    if ((st = rt_query_overlaps(r, r->q.probe.p, 1, k, 0, r->q.overlap_idx.p, r->q.overlap_count.p, hs,
+                                nullptr)))
+        return st;
+    uint32_t idx[RT_OVERLAP_MAX], count = 0;
+    RT_HIP(r, hipMemcpyAsync(idx, r->q.overlap_idx.p, k * sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipMemcpyAsync(&count, r->q.overlap_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    memcpy(indices_out, idx, k * sizeof(uint32_t));
+    if (count_out) *count_out = count;
+    return RT_OK;
+}
+
+// First-hit G-buffer of the current camera: no
+// fill_frame_args (which advances the frame id and the sums), nothing of the
+// frames' framebuffer.
+int rt_render_gbuffer(rt_renderer* r, const rt_gbuffer* out, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_render_gbuffer: null handle");
+    if (!out || (!out->dev_hits && !out->dev_normals && !out->dev_albedo))
+        return fail(r, RT_E_INVALID, "rt_render_gbuffer: no output buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_render_gbuffer: no scene (rt_set_scene first)");
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    // ... and the camera and size (rt_gbuffer.hip)
+    fill_camera(r, a.cam);
+    a.W = r->W;
+    a.H = r->H;
+    // the frames' own albedo table: whichever of the two runs first makes it,
+    // here ahead of the stats bracket (its launch is not the G-buffer's time)
+    if (out->dev_albedo && (st = ensure_prim_al(r, a.sc, hs))) return st;
+    st = query_launch(r, "rt_render_gbuffer", hs, stats, [&](unsigned long long* ctr) {
+        return launch_gbuffer(a, out->dev_hits, out->dev_normals, out->dev_albedo, ctr, hs);
+    });
+    if (!st && stats) stats->primary_rays = static_cast<uint64_t>(r->W) * r->H;
+    return st;
+}
+
+}  // extern "C"

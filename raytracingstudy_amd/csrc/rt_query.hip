@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_params.h"
+#include "rt_query_common.h"
 #include "rt_walk.h"
 
 namespace rtamd {
@@ -21,12 +22,6 @@ struct QueryArgs {
     unsigned long long* counters; // stats launches: 8 lines of kStatLineStride words
 };
 
-__device__ __forceinline__ unsigned long long query_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // One ray per lane, 256-thread blocks; a ray is two coalesced dwordx4 loads,
 // a hit one dwordx2 store.  FrameArgs leads the argument block although the
 // generic walk compiles every kernargs() read out (rt_walk.h): kernargs()
@@ -35,6 +30,7 @@ __device__ __forceinline__ unsigned long long query_wave_sum(unsigned long long 
 // fields (zero camera and screens), not another struct's bytes.
 // The dynamic LDS is the per-lane ancestor stack alone: [level][thread],
 // stack_levels(a.sc) levels (launch_query sizes it).
+// (rt_query_common.h holds what is shared; the stack and the flush stay here: a helper moves registers in the stats instances)
 template <bool kAny, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) query_kernel(FrameArgs a, QueryArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -65,10 +61,6 @@ __global__ void __launch_bounds__(kBlockThreads) query_kernel(FrameArgs a, Query
     }
 }
 
-size_t query_lds_bytes(const SceneArgs& sc) {
-    return static_cast<size_t>(stack_levels(sc)) * kBlockThreads * sizeof(uint2);
-}
-
 // a.sc is the scene; the rest of `a` is unused by the kernel (see above).
 // counters != null: a stats launch (the caller zeroed its 8 lines).
 hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32_t n, bool any,
@@ -79,9 +71,8 @@ hipError_t launch_query(const FrameArgs& a, const void* rays, void* hits, uint32
     q.hits = static_cast<uint2*>(hits);
     q.n = n;
     q.counters = counters;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(n) + kBlockThreads - 1u) / kBlockThreads));
-    const dim3 block(kBlockThreads);
-    const size_t lds = query_lds_bytes(a.sc);
+    const dim3 grid = query_grid(n), block(kBlockThreads);
+    const size_t lds = query_stack_bytes(stack_levels(a.sc));
     if (counters) {
         if (any) hipLaunchKernelGGL((query_kernel<true, true>), grid, block, lds, st, a, q);
         else hipLaunchKernelGGL((query_kernel<false, true>), grid, block, lds, st, a, q);

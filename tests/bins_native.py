@@ -56,5 +56,5 @@ def rects(dump, sp, pose, K, w, h, shrink=1.0):
 
 def frame_gate(dump, pose, K, w, h):
     """Whether a w x h frame of this camera may use bins: the host's gate
-    (bins_camera_ok and cam8_basis, rt_frame.cpp screen_bins)."""
+    (bins_camera_ok and cam8_basis, rt_bins_host.cpp screen_bins)."""
     return dump("framegate", w, h, *cam_args(pose, K)).strip() == "1"

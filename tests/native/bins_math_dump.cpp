@@ -4,7 +4,14 @@
 //         {cx, cy, cz, r} records): class x0 y0 x1 y1 near(f32 bits)
 //   camok K[9] R[9] o[3]                       -> 0 | 1
 //   framegate W H K[9] R[9] o[3]               -> 0 | 1: the host's gate of a W x H
-//         frame (rt_frame.cpp screen_bins: bins_camera_ok and cam8_basis)
+//         frame (rt_bins_host.cpp screen_bins: bins_camera_ok and cam8_basis)
+//   cadence gen,mframe,mflag ...               -> per plain frame "skip" | "build": the
+//         dense-skip step (bin_dense_skip_step) over frames 1, 2, ... of scene
+//         generation `gen`, each seeing the pinned frame and flag words mframe and
+//         mflag; a frame that builds becomes the last building frame, as in
+//         rt_bins_host.cpp screen_bins
+//   want captest n mframe mflag mentries lastframe ent_n -> the entries wanted
+//         (bin_entries_wanted)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -82,6 +89,24 @@ int main(int argc, char** argv) {
         vec(R, 9);
         vec(o, 3);
         printf("%d\n", rtamd::bins_camera_ok(K, R, o) && rtamd::cam8_basis(K, R, W, H, B) ? 1 : 0);
+    } else if (cmd == "cadence") {
+        rtamd::BinCadence c;
+        for (uint32_t frame = 1; g_next < g_argc; ++frame) {
+            unsigned long long gen;
+            unsigned mframe, mflag;
+            if (sscanf(arg(), "%llu,%u,%u", &gen, &mframe, &mflag) != 3) {
+                fprintf(stderr, "bins_math_dump: cadence takes gen,mframe,mflag\n");
+                return 2;
+            }
+            const bool skip = rtamd::bin_dense_skip_step(c, gen, mframe, mflag);
+            if (!skip) c.last_frame = frame;
+            printf("%s\n", skip ? "skip" : "build");
+        }
+    } else if (cmd == "want") {
+        const uint32_t captest = u32(), n = u32(), mframe = u32(), mflag = u32(), mentries = u32(),
+                       lastframe = u32();
+        const size_t ent_n = strtoull(arg(), nullptr, 10);
+        printf("%zu\n", rtamd::bin_entries_wanted(captest, n, mframe, mflag, mentries, lastframe, ent_n));
     } else {
         fprintf(stderr, "bins_math_dump: unknown command '%s'\n", cmd.c_str());
         return 2;

@@ -147,7 +147,7 @@ def model(seed, dump, orc, hits=True):
         elif not frame_gate(dump, c["pose"], c["K"], c["w"], c["h"]):
             reason = "camera"
         elif entries > 6 * c["n"] + 65536:
-            reason = "capacity"    # (the first frame's entry buffer, rt_frame.cpp screen_bins)
+            reason = "capacity"    # (the first frame's entry buffer, rt_bins_host.cpp screen_bins)
         elif wide > WIDE_CAP:
             reason = "wide"
         else:
