@@ -283,7 +283,8 @@ test_flags = 0
 # the sources the scene kernel's machine code is built from (device code and
 # its compile flags): a PMC summary is valid for a build iff its stamp matches
 # (csrc/rt_query_common.h is not one: only the four query units include it,
-# it does not reach rt_kernels.hip)
+# it does not reach rt_kernels.hip; nor is csrc/rt_compat.hip: the compat and
+# unpack kernels are a unit of their own, no scene kernel is built from it)
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_shade.h", "csrc/rt_sorted.h", "csrc/rt_walk.h", "csrc/rt_bins.h",
                   "csrc/rt_bins_math.h", "csrc/screen_bins.hip", "csrc/rt_params.h", "csrc/rt_sched.h",
                   "csrc/Makefile")

@@ -10,10 +10,11 @@ using namespace rtamd;
 namespace {
 
 // Whether this frame builds bins; bins.last_reason says why not.
-bool bins_gate(rt_renderer* r, const FrameArgs& a) {
+bool bins_gate(rt_renderer* r, const FrameArgs& a, const FramePlan& plan) {
     ScreenBinState& s = r->bins;
     if (r->cfg.flags & RT_FLAG_NO_BINS) return s.last_reason = RT_BINS_OFF_FLAG, false;
-    if (a.count_work || !frame_reads_bins(a, r->sort_rounds) ||
+    // (the scene_kernel_w8 instances read bins: plain frames of the wave queue)
+    if (a.count_work || !plan.inst.w8() ||
         static_cast<uint64_t>(a.W) * a.H * a.spp < s.min_samples)
         return s.last_reason = RT_BINS_OFF_KERNEL, false;
     float B[9];
@@ -63,7 +64,8 @@ int bins_buffers(rt_renderer* r, const FrameArgs& a, uint32_t nb, hipStream_t st
 }
 
 // The build's arguments: the scene, the frame's camera and wave tile, the buffers.
-BinBuild bins_build_args(const rt_renderer* r, const FrameArgs& a, uint32_t nbx, uint32_t nby) {
+BinBuild bins_build_args(const rt_renderer* r, const FrameArgs& a, const FramePlan& plan, uint32_t nbx,
+                         uint32_t nby) {
     const ScreenBinState& s = r->bins;
     const uint32_t nb = nbx * nby;
     BinBuild b{};
@@ -77,11 +79,8 @@ BinBuild bins_build_args(const rt_renderer* r, const FrameArgs& a, uint32_t nbx,
     b.H = a.H;
     b.nbx = nbx;
     b.nby = nby;
-    {  // the wave tile launch_scene gives this frame's kernel
-        const WaveGrid grid(a.W, a.H, a.spp, a.tiles ? a.n_tiles : 0u, a.tile_size);
-        b.tw = grid.tw;
-        b.th = grid.th;
-    }
+    b.tw = plan.grid.tw;
+    b.th = plan.grid.th;
     b.shrink = s.shrink;
     b.capacity = static_cast<uint32_t>(s.ent.n / 2);
     b.cap = s.cap;
@@ -135,7 +134,7 @@ int bins_launch(rt_renderer* r, FrameArgs& a, const BinBuild& b, hipStream_t st)
 // the frame kernel: built by every plain frame whose kernel reads them, never
 // keyed on the pose (the Displayer's camera moves every frame), with no wait
 // and no readback.
-int rtamd::screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
+int rtamd::screen_bins(rt_renderer* r, FrameArgs& a, const FramePlan& plan, hipStream_t st) {
     a.bin_hdr = nullptr;
     a.bin_ent = nullptr;
     a.bin_nb = 0;
@@ -143,10 +142,10 @@ int rtamd::screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st) {
     a.bin_info = nullptr;
     a.bin_nbx = 0;
     r->bins.timed = false;
-    if (!bins_gate(r, a)) return RT_OK;
+    if (!bins_gate(r, a, plan)) return RT_OK;
     const uint32_t nbx = (a.W + kBinSide - 1u) / kBinSide, nby = (a.H + kBinSide - 1u) / kBinSide;
     if (const int ost = bins_buffers(r, a, nbx * nby, st)) return ost;
-    return bins_launch(r, a, bins_build_args(r, a, nbx, nby), st);
+    return bins_launch(r, a, bins_build_args(r, a, plan, nbx, nby), st);
 }
 
 extern "C" {

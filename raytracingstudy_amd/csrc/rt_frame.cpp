@@ -148,18 +148,18 @@ int poison_outputs(rt_renderer* r, const FrameArgs& a, hipStream_t st) {
 // ---- do_render's steps, in its order: each queues on `st` and fills its part of `a` ----
 
 // Step 1: this frame's counter set (RendererState::ctr_set) and, for the wave
-// queue, its per-XCD slot table (8 x (superblocks + 2) words after the
+// queue, its per-XCD slot table (8 x plan->slot_stride words after the
 // counters), zero when the kernel starts; the other set is the one the kernel
 // zeroes for the next frame.  counters_after_launch is the other half.
-int frame_counters(rt_renderer* r, FrameArgs& a, hipStream_t st) {
-    const bool scene = r->cfg.mode == RT_MODE_SCENE;
+// plan: a scene frame's, null for a compat frame.
+int frame_counters(rt_renderer* r, FrameArgs& a, const FramePlan* plan, hipStream_t st) {
+    const bool scene = plan != nullptr;
     size_t words = kCounterWords;  // one set
     a.wq_slots = nullptr;
     a.wq_slot_stride = 0;
     if (scene) {
-        const WaveGrid grid(a.W, a.H, a.spp, a.tiles ? a.n_tiles : 0u, a.tile_size);
-        a.wq_slot_shift = grid.slot_shift();
-        a.wq_slot_stride = (a.wq_slot_shift == 12u ? grid.superblocks() : grid.blocks()) + 2u;
+        a.wq_slot_shift = plan->slot_shift;
+        a.wq_slot_stride = plan->slot_stride;
         words += (8u * static_cast<size_t>(a.wq_slot_stride) + 1u) / 2u;
     }
     if (r->ctr_stride < words) {  // (re)allocate both sets and zero them
@@ -194,11 +194,10 @@ void counters_after_launch(rt_renderer* r, const FrameArgs& a, bool launched) {
 
 // Step 2: the superblock claim order of a full frame (RT_SB_ORDER=1, a test
 // hook), uploaded when the superblock grid changes.
-int superblock_order(rt_renderer* r, FrameArgs& a, hipStream_t) {
+int superblock_order(rt_renderer* r, FrameArgs& a, const FramePlan* plan, hipStream_t) {
     a.sb_order = nullptr;
-    if (r->cfg.mode != RT_MODE_SCENE || a.tiles || a.wq_slot_shift != 12u || !r->sb_hilbert) return RT_OK;
-    const WaveGrid grid(a.W, a.H, a.spp, 0u, 0u);
-    const uint32_t nx = grid.nsx, ny = grid.nsy;  // the superblock grid of this frame
+    if (!plan || a.tiles || plan->slot_shift != 12u || !r->sb_hilbert) return RT_OK;
+    const uint32_t nx = plan->grid.nsx, ny = plan->grid.nsy;  // the superblock grid of this frame
     if (r->sb_nx != nx || r->sb_ny != ny || !r->sb_order.p) {
         const std::vector<uint32_t> ord = hilbert_order(nx, ny);
         if (const int ost = ensure(r, r->sb_order, ord.size())) return ost;
@@ -372,10 +371,10 @@ inline int block_stats_end(rt_renderer*, const FrameArgs&, hipStream_t) { return
 #endif
 
 // Step 5: poison (test only), launch, and the renderer's bookkeeping of a queued frame.
-int launch_frame(rt_renderer* r, FrameArgs& a, hipStream_t st) {
+int launch_frame(rt_renderer* r, FrameArgs& a, const FramePlan* plan, hipStream_t st) {
     int ost;
     if ((ost = timeline_begin(r, a, st)) || (ost = block_stats_begin(r, a, st))) return ost;
-    hipError_t e = r->cfg.mode == RT_MODE_SCENE ? launch_scene(a, r->sort_rounds, st) : launch_compat(a, st);
+    hipError_t e = plan ? launch_scene(a, *plan, st) : launch_compat(a, st);
     counters_after_launch(r, a, e == hipSuccess);
     if (e != hipSuccess) return hip_fail(r, e, "kernel launch");
     if ((ost = block_stats_end(r, a, st)) || (ost = mark_queued(r, st))) return ost;
@@ -413,10 +412,17 @@ int rtamd::do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats
     const bool scene = r->cfg.mode == RT_MODE_SCENE;
     if (scene && !r->has_scene)
         return fail(r, RT_E_NOSCENE, "RT_MODE_SCENE render without rt_set_scene");
+    a.count_work = stats ? 1u : 0u;
+    // a scene frame's plan, made once: its kernel instance, wave-tile grid,
+    // slot table, LDS bytes and ticket size (rt_sched.h); the steps read it
+    const FramePlan planned = plan_scene_frame(a.variant, a.spp, a.accum != nullptr, stats != nullptr,
+                                               r->sort_rounds, a.sc.tab_k, a.sc.stack_depth, a.W, a.H,
+                                               a.tiles ? a.n_tiles : 0u, a.tile_size, a.sc.opt);
+    const FramePlan* plan = scene ? &planned : nullptr;
     int ost;
     if ((ost = order_after_last(r, st))) return ost;
-    if ((ost = frame_counters(r, a, st))) return ost;
-    if ((ost = superblock_order(r, a, st))) return ost;
+    if ((ost = frame_counters(r, a, plan, st))) return ost;
+    if ((ost = superblock_order(r, a, plan, st))) return ost;
     if (scene) {
         if ((ost = camera_records(r, a, st))) return ost;
         if ((ost = light_records(r, a, st))) return ost;  // (and the occluder lists)
@@ -426,15 +432,14 @@ int rtamd::do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats
         if ((ost = ensure_prim_al(r, a.sc, st))) return ost;
     }
     if ((ost = poison_outputs(r, a, st))) return ost;
-    a.count_work = stats ? 1u : 0u;
     if (scene) {
-        if ((ost = screen_bins(r, a, st))) return ost;  // (step 4b: rt_bins_host.cpp)
+        if ((ost = screen_bins(r, a, *plan, st))) return ost;  // (step 4b: rt_bins_host.cpp)
     } else {
         r->bins.last_reason = RT_BINS_OFF_KERNEL;
     }
     a.test_fault_queue = r->test_fault_queue && !stats ? 1u : 0u;
     if (stats) RT_HIP(r, hipEventRecord(r->ev0, st));
-    if ((ost = launch_frame(r, a, st))) return ost;
+    if ((ost = launch_frame(r, a, plan, st))) return ost;
     return stats ? frame_stats(r, a, st, stats) : RT_OK;
 }
 

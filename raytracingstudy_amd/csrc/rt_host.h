@@ -3,7 +3,8 @@
 // stream-ordering helpers, and the functions the units call across.
 //   rt_capi.cpp   handle lifetime, camera, rt_render and the display binding
 //   rt_scene.cpp  scene upload, octree build, exports
-//   rt_frame.cpp  per-frame preparation and launch (do_render's steps), tiles
+//   rt_frame.cpp  per-frame preparation and launch (do_render's steps: it plans a
+//                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
 //   rt_queries.cpp    ray, multi-hit and overlap queries, picking, the G-buffer
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
@@ -29,13 +30,16 @@ struct ncclComm;  // <rccl/rccl.h>'s ncclComm_t is a pointer to it; only rt_mult
 
 namespace rtamd {
 
-// the kernels' launchers (rt_kernels.hip, rt_query.hip, rt_gbuffer.hip)
-hipError_t launch_compat(const FrameArgs& a, hipStream_t st);
-hipError_t launch_scene(const FrameArgs& a, bool sort, hipStream_t st);
+// the kernels' launchers
+// rt_kernels.hip: a scene frame as do_render planned it (plan_scene_frame, rt_sched.h)
+hipError_t launch_scene(const FrameArgs& a, const FramePlan& plan, hipStream_t st);
 bool variant_available(uint32_t v);
+// rt_compat.hip: the reference's frame restated; packed tiles scattered into the frame
+hipError_t launch_compat(const FrameArgs& a, hipStream_t st);
 hipError_t launch_unpack(const uint32_t* packed, const uint32_t* tiles, uint32_t n_tiles,
                          uint32_t ts, uint32_t tiles_x, uint32_t W, uint32_t H, uint32_t* img,
                          hipStream_t st);
+// rt_records.hip: the per-reference records
 hipError_t launch_cam_screen(const float4* prim_sp, uint32_t n, const float o[3], float4* out,
                              hipStream_t st);
 hipError_t launch_shd_screen(const float4* prim_sp, uint32_t n, const float e[6], double delta,
@@ -68,7 +72,7 @@ struct BinBuild {
     uint32_t n_spheres;
     float K[9], R[9], o[3];     // the frame's camera (CamArgs)
     uint32_t W, H, nbx, nby;
-    uint32_t tw, th;            // the frame's wave tile (WaveGrid): powers of two, <= 8
+    uint32_t tw, th;            // the frame's wave tile (FramePlan::grid): powers of two, <= 8
     double shrink;             // 1; 0.9 under the test hook RT_TEST_BIN_SHRINK
     uint32_t capacity;          // entries `ent` holds
     uint32_t cap;               // a bin over it walks (<= kBinCap)
@@ -92,9 +96,6 @@ hipError_t launch_first_refs(const float4* prim_sp, const uint32_t* prim_idx, ui
                              hipStream_t st);
 size_t bins_scan_temp_bytes(uint32_t n_items);
 hipError_t launch_screen_bins(const BinBuild& b, hipStream_t st);
-// rt_kernels.hip: whether launch_scene would run this frame on an instance
-// that reads bins (the scene_kernel_w8 instances: plain frames of the wave queue)
-bool frame_reads_bins(const FrameArgs& a, bool sort);
 
 // rt_last_error(NULL): the calling thread's last failure without a handle
 extern thread_local std::string g_last_error;
@@ -429,7 +430,7 @@ inline void sum_stat_lines(const unsigned long long* lines, unsigned long long c
         for (uint32_t i = 0; i < 4; ++i) c[i] += lines[q * kStatLineStride + i];
 }
 // rt_bins_host.cpp: do_render's step 4b
-int screen_bins(rt_renderer* r, FrameArgs& a, hipStream_t st);
+int screen_bins(rt_renderer* r, FrameArgs& a, const FramePlan& plan, hipStream_t st);
 // rt_multi.cpp: a multi-device handle's part of the calls above
 int multi_render(rt_renderer* r, uint32_t* out, hipStream_t hs, rt_stats* stats);
 int multi_wait(rt_renderer* r);

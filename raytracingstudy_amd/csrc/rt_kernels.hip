@@ -1,22 +1,21 @@
-// rt_kernels.hip — hand-written HIP kernels for gfx950 (MI355X, CDNA4).
-//
-// Replaces the reference's single CUDA kernel `raytracing`
-// (src/renderer.cu:57-82, grid (W/32+1, H/32+1) x block (32,32)) and its
-// <<<1,1>>> setup kernels (src/renderer.cu:84-109):
-//   * compat_kernel : byte-exact restatement of `raytracing` (root-box slab
-//                     test, R = Octree::traverse() = 200, miss colour).
-//   * scene_kernel  : the build-defined octree path (DESIGN.md "Scene mode"):
-//                     here its two schedulers; what a wave does per tile is
-//                     in rt_shade.h and rt_sorted.h.
-//   * unpack_kernel : scatters packed per-rank tiles into the frame.
-// The launchers follow; the per-reference record kernels are rt_records.hip.
+// rt_kernels.hip — the scene kernels, hand-written HIP for gfx950 (MI355X,
+// CDNA4): the build-defined octree path (DESIGN.md "Scene mode") that stands
+// where the reference has its single CUDA kernel `raytracing`
+// (src/renderer.cu:57-82) and its <<<1,1>>> setup kernels (src/renderer.cu:84-109).
+//   * scene_body   : its two schedulers (block-tile queue, two-level wave
+//                    queue); what a wave does per tile is in rt_shade.h and
+//                    rt_sorted.h.
+//   * scene_kernel, scene_kernel_w8 : the entry points, and the table of the
+//                    instances that exist (launch_flags).
+//   * launch_scene : the launch of a planned frame (FramePlan, rt_sched.h).
+// Nothing else: the byte-exact restatement of `raytracing` and the tile unpack
+// are rt_compat.hip, the per-reference record kernels rt_records.hip.
 // Compiled with -ffp-contract=off: every f32/f64 expression is evaluated in
 // source order with IEEE division/sqrt, exactly like oracle/oracle.c.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
-#include <utility>
 #include <vector>
 
 #include "rt_params.h"
@@ -24,85 +23,6 @@
 #include "rt_sorted.h"  // scene mode: quadrant-sorted rounds
 
 namespace rtamd {
-
-// src/renderer.cu:3-55 — `hit_sphere`: slab test of the root box [0,1.28]^3
-// with the negative-direction axes mirrored about the centre 0.64 (f32
-// origin/inverse widened to f64, f64 slab products rounded to f32, NaN-dropping
-// fmaxf/fminf, no t >= 0 test).
-__device__ __forceinline__ double mirror_o(float o, float d) {
-    return d < 0.0f ? static_cast<double>(0.64f * 2.0f - o) : static_cast<double>(o);
-}
-__device__ __forceinline__ double mirror_inv(float d) {
-    return d < 0.0f ? static_cast<double>(-(1.0f / d)) : static_cast<double>(1.0f / d);
-}
-__device__ __forceinline__ bool hit_root_box(const float o[3], float d0, float d1, float d2) {
-    const double bmin = static_cast<double>(0.0f);
-    const double bmax = static_cast<double>(1.28f);
-    const double rx = mirror_o(o[0], d0), ry = mirror_o(o[1], d1), rz = mirror_o(o[2], d2);
-    const double ix = mirror_inv(d0), iy = mirror_inv(d1), iz = mirror_inv(d2);
-    const float tx0 = static_cast<float>((bmin - rx) * ix);
-    const float tx1 = static_cast<float>((bmax - rx) * ix);
-    const float ty0 = static_cast<float>((bmin - ry) * iy);
-    const float ty1 = static_cast<float>((bmax - ry) * iy);
-    const float tz0 = static_cast<float>((bmin - rz) * iz);
-    const float tz1 = static_cast<float>((bmax - rz) * iz);
-    return fmaxf(fmaxf(tx0, ty0), tz0) < fminf(fminf(tx1, ty1), tz1);
-}
-
-// getRay under ONE CANDIDATE contraction of include/camera.h:31-34 (dz = 1
-// folds; an fadd of two products fused through its first operand), a guess at
-// what nvcc's default -fmad=true does to the reference binary.  Which order
-// that binary really uses cannot be checked without nvcc: unpinned
-// (DESIGN.md 2.1).  The default (get_ray) is the SOURCE semantics.  Same
-// operations as the oracle's contracted getRay, contract = 1.
-__device__ __forceinline__ void get_ray_fma(const CamArgs& c, float u, float v, float& wx,
-                                            float& wy, float& wz) {
-    const float dx = (u - c.K[2]) / c.K[0];
-    const float dy = (v - c.K[5]) / c.K[4];
-    wx = fmaf(c.R[0], dx, c.R[3] * dy) + c.R[6];
-    wy = fmaf(c.R[1], dx, c.R[4] * dy) + c.R[7];
-    wz = fmaf(c.R[2], dx, c.R[5] * dy) + c.R[8];
-    const float len = sqrtf(fmaf(wz, wz, fmaf(wx, wx, wy * wy)));
-    wx /= len;
-    wy /= len;
-    wz /= len;
-}
-
-__device__ __forceinline__ uint32_t compat_pixel(const CamArgs& cam, uint32_t x, uint32_t y,
-                                                 uint32_t contract) {
-    float d0, d1, d2;
-    if (contract)
-        get_ray_fma(cam, static_cast<float>(x), static_cast<float>(y), d0, d1, d2);
-    else
-        get_ray(cam, static_cast<float>(x), static_cast<float>(y), d0, d1, d2);
-    if (hit_root_box(cam.o, d0, d1, d2)) return 0xFFFFFFFFu;
-    const uint32_t g = static_cast<uint32_t>(sat(d1) * 255.0f);
-    const uint32_t b = static_cast<uint32_t>(sat(d2) * 255.0f);
-    return 200u | (g << 8) | (b << 16) | (255u << 24);
-}
-
-// One wave = 64 consecutive pixels of a row; one packed 32-bit store per lane.
-__global__ void __launch_bounds__(kBlockThreads) compat_kernel(FrameArgs a) {
-    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u);
-    const uint32_t y = blockIdx.y * 4u + (threadIdx.x >> 6);
-    if (x >= a.W || y >= a.H) return;
-    __builtin_nontemporal_store(compat_pixel(a.cam, x, y, a.contract), a.out8 + (size_t)y * a.W + x);
-}
-
-// Tile-packed compat: block = 64 x 4 strip of one tile.
-__global__ void __launch_bounds__(kBlockThreads) compat_tiles_kernel(FrameArgs a) {
-    const uint32_t ts = a.tile_size;
-    const uint32_t strips = ts / 4u * (ts / 64u);
-    const uint32_t k = blockIdx.x / strips;
-    const uint32_t sidx = blockIdx.x % strips;
-    const uint32_t lx = (sidx % (ts / 64u)) * 64u + (threadIdx.x & 63u);
-    const uint32_t ly = (sidx / (ts / 64u)) * 4u + (threadIdx.x >> 6);
-    const uint32_t tile = a.tiles[k];
-    const uint32_t x = (tile % a.tiles_x) * ts + lx;
-    const uint32_t y = (tile / a.tiles_x) * ts + ly;
-    const uint32_t v = (x < a.W && y < a.H) ? compat_pixel(a.cam, x, y, a.contract) : 0u;
-    a.out8[(size_t)k * ts * ts + ly * ts + lx] = v;
-}
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
@@ -472,167 +392,87 @@ __global__ void __launch_bounds__(kBlockThreads, 8) __attribute__((amdgpu_num_sg
     scene_body<C>(a);
 }
 
-__global__ void __launch_bounds__(kBlockThreads)
-    unpack_kernel(const uint32_t* __restrict__ packed, const uint32_t* __restrict__ tiles,
-                  uint32_t n_tiles, uint32_t ts, uint32_t tiles_x, uint32_t W, uint32_t H,
-                  uint32_t* __restrict__ img) {
-    const size_t i = (size_t)blockIdx.x * kBlockThreads + threadIdx.x;
-    const size_t per = (size_t)ts * ts;
-    if (i >= per * n_tiles) return;
-    const uint32_t k = static_cast<uint32_t>(i / per);
-    const uint32_t r = static_cast<uint32_t>(i % per);
-    const uint32_t tile = tiles[k];
-    if (tile == 0xFFFFFFFFu) return;  // RT_TILE_SKIP: a padding slot
-    const uint32_t x = (tile % tiles_x) * ts + r % ts;
-    const uint32_t y = (tile / tiles_x) * ts + r / ts;
-    if (x < W && y < H) img[(size_t)y * W + x] = packed[i];
-}
-
 // ---------------------------------------------------------------------------
-// launchers (called from rt_capi.cpp)
+// launch_scene (called from rt_frame.cpp): the frame's plan (FramePlan,
+// rt_sched.h) and the device's occupancy numbers size the launch
 // ---------------------------------------------------------------------------
 
-hipError_t launch_compat(const FrameArgs& a, hipStream_t st) {
-    if (a.tiles) {
-        const uint32_t strips = a.tile_size / 4u * (a.tile_size / 64u);
-        hipLaunchKernelGGL(compat_tiles_kernel, dim3(a.n_tiles * strips), dim3(kBlockThreads), 0,
-                           st, a);
-    } else {
-        hipLaunchKernelGGL(compat_kernel, dim3((a.W + 63) / 64, (a.H + 3) / 4), dim3(kBlockThreads),
-                           0, st, a);
-    }
-    return hipGetLastError();
-}
-
-// Resident workgroups on the device for a kernel at a given LDS size.  The
-// occupancy query is a host call: cache it per (kernel, LDS bytes, device) so
-// the launch path stays a single hipLaunchKernelGGL.
-template <typename K>
-static uint32_t resident_blocks(K kernel, size_t lds) {
-    struct Key {
+// What a device holds: its CUs and, per (kernel, LDS bytes), the resident
+// workgroups.  The queries are host calls: cached per device, so the launch
+// path stays a single hipLaunchKernelGGL.
+struct Occupancy {
+    uint32_t resident, cus;
+};
+static Occupancy occupancy(const void* kernel, size_t lds) {
+    struct Kernel {
         const void* k;
         size_t lds;
+        uint32_t resident;
+    };
+    struct Device {
         int dev;
+        uint32_t cus;
+        std::vector<Kernel> kernels;
     };
     static std::mutex mu;
-    static std::vector<std::pair<Key, uint32_t>> cache;
+    static std::vector<Device> devices;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const void* kp = reinterpret_cast<const void*>(kernel);
-    {
-        std::lock_guard<std::mutex> g(mu);
-        for (const auto& e : cache)
-            if (e.first.k == kp && e.first.lds == lds && e.first.dev == dev) return e.second;
+    std::lock_guard<std::mutex> g(mu);
+    auto d = std::find_if(devices.begin(), devices.end(), [dev](const Device& e) { return e.dev == dev; });
+    if (d == devices.end()) {
+        hipDeviceProp_t prop;
+        const uint32_t cus = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
+        d = devices.insert(d, Device{dev, cus, {}});
     }
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    for (const Kernel& e : d->kernels)
+        if (e.k == kernel && e.lds == lds) return {e.resident, d->cus};
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlockThreads, lds) != hipSuccess ||
         per_cu <= 0)
         per_cu = 4;
-    const uint32_t n = static_cast<uint32_t>(cus * per_cu);
-    std::lock_guard<std::mutex> g(mu);
-    cache.push_back({{kp, lds, dev}, n});
-    return n;
-}
-
-static uint32_t cus_of_device() {
-    static std::mutex mu;
-    static std::vector<std::pair<int, uint32_t>> cache;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> g(mu);
-    for (const auto& e : cache)
-        if (e.first == dev) return e.second;
-    hipDeviceProp_t prop;
-    const uint32_t n = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    cache.push_back({dev, n});
-    return n;
-}
-
-constexpr size_t kOneSppLds = (160u * 1024u / 3u) & ~size_t(15);  // 3 workgroups per CU
-
-// Block tiles in the frame (or in the packed tile list) for block-tile side b.
-static uint32_t count_block_tiles(const FrameArgs& a, uint32_t b) {
-    if (a.tiles) return a.n_tiles * (a.tile_size / b) * (a.tile_size / b);
-    return ((a.W + b - 1) / b) * ((a.H + b - 1) / b);
-}
-
-// Persistent launch: grid = resident workgroups; the block-tile side shrinks
-// (16 -> 8 -> 4 pixels, never below two wave tiles) until the tile queue holds
-// >= 8 tiles per resident workgroup, so the dynamic queue can even out costly
-// image regions to the end (A/B, profiles/r01/bts_ab.log: 1080p 64 spp picks
-// 8x8 tiles, -6.4% vs 16x16; a 1/4 or 1/8 multi-GPU share picks 4x4).
-template <typename K>
-static void launch_persistent(K kernel, const FrameArgs& a_in, size_t lds, hipStream_t st) {
-    FrameArgs a = a_in;
-    // 1 spp: a wave's 64 lanes are 64 different pixels, whose walks thrash
-    // the L1 when 5 workgroups share a CU; the dynamic LDS is padded so that
-    // at most 3 are resident (C2: 0.358 -> 0.274 ms; 2 or 4 per CU slower,
-    // 4 spp unchanged; profiles/r01/c2_wg_cap_ab.log)
-    if (a.spw == 1u && !(a.sc.opt & kOptNoWgCap)) lds = std::max(lds, kOneSppLds);
-    const uint32_t res = resident_blocks(kernel, lds);
-    const uint32_t min_side = 2u * std::max(a.tw, a.th);
-    a.bts = kTileSide;
-    const uint32_t force = (a.sc.opt >> kOptBtsShift) & 7u;
-    if (force && (kTileSide >> (force - 1u)) >= min_side)
-        a.bts = kTileSide >> (force - 1u);
-    else
-        while (a.bts / 2u >= min_side && count_block_tiles(a, a.bts) < 8u * res) a.bts /= 2u;
-    const uint32_t grid = std::min(count_block_tiles(a, a.bts), res);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, st, a);
-}
-
-// Per-wave queue launch: grid = resident workgroups, capped by the work.
-template <typename K>
-static void launch_waveq(K kernel, const FrameArgs& a, size_t lds, hipStream_t st, uint32_t per_simd) {
-    const uint32_t res = resident_blocks(kernel, lds);
-    const uint64_t units = WaveGrid(a.W, a.H, a.spp, a.tiles ? a.n_tiles : 0u, a.tile_size).units();
-    // (the grid only sizes the launch; padding units of edge blocks are skipped)
-    const uint64_t want = (units + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
-    // The occupancy query counts 8 workgroups per CU for the 7-wave builds
-    // (60-65 VGPRs), but their 94 SGPRs leave room for 7: the 8th per CU
-    // only starts when another exits, finds nothing and adds 8 queue atomics
-    // to the tail (profiles/r02/timeline_hwid.log).  Capped at the build's
-    // waves per SIMD: C3 -0.8%, 1/8 share -5% (profiles/r02/steal_ab.log,
-    // measured with the static per-XCD ranges that preceded the two-level queue)
-    const uint64_t cap = per_simd ? static_cast<uint64_t>(cus_of_device()) * per_simd : res;
-    const uint32_t grid =
-        static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(res, cap), want)));
-    FrameArgs b = a;
-    if (!((a.sc.opt >> kOptChunkShift) & 7u)) {
-        // auto ticket size, second half: a small launch (a multi-GPU share)
-        // has few units per wave, and big tickets lengthen its tail. N-way
-        // C3 shares: 4 per ticket best at 1/2 and 1/4, 2 at 1/8 (36 units a
-        // wave; profiles/r01/shard_chunk.log)
-        const uint64_t per_wave = units / (static_cast<uint64_t>(grid) * (kBlockThreads / 64));
-        const uint32_t cap = per_wave >= 64 ? 4u : per_wave >= 16 ? 2u : 1u;
-        b.wq_chunk = std::min(b.wq_chunk, cap);
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, st, b);
+    d->kernels.push_back({kernel, lds, d->cus * static_cast<uint32_t>(per_cu)});
+    return {d->kernels.back().resident, d->cus};
 }
 
 // One instance: the 8-wave build for plain wave-queue frames, scene_kernel
-// for the rest; each queue has its launcher.
+// for the rest; each queue has its sizing (rt_sched.h).
 template <class C>
-static void launch_instance(const FrameArgs& a, size_t lds, hipStream_t st) {
+static auto instance_kernel() {
     if constexpr (C::min_waves == 8)
-        launch_waveq(scene_kernel_w8<C>, a, lds, st, C::min_waves);
-    else if constexpr (C::waveq)
-        launch_waveq(scene_kernel<C>, a, lds, st, C::min_waves);
+        return scene_kernel_w8<C>;
     else
-        launch_persistent(scene_kernel<C>, a, lds, st);
+        return scene_kernel<C>;
+}
+template <class C>
+static void launch_instance(FrameArgs a, const FramePlan& p, hipStream_t st) {
+    const auto kernel = instance_kernel<C>();
+    const size_t lds = C::waveq ? p.lds_bytes : block_tile_lds(p.lds_bytes, p.spw, a.sc.opt);
+    const Occupancy o = occupancy(reinterpret_cast<const void*>(kernel), lds);
+    uint32_t grid;
+    if constexpr (C::waveq) {
+        const WaveQueueLaunch s =
+            size_wave_queue(p.grid.units(), o.resident, o.cus, C::min_waves, p.ticket, p.ticket_forced);
+        a.wq_chunk = s.ticket;
+        grid = s.grid;
+    } else {
+        const BlockTileLaunch s =
+            size_block_tiles(a.W, a.H, a.tiles ? a.n_tiles : 0u, a.tile_size, p.grid.tw, p.grid.th,
+                             o.resident, (a.sc.opt >> kOptBtsShift) & 7u);
+        a.bts = s.side;
+        grid = s.grid;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), lds, st, a);
 }
 
 // SceneInstance -> compiled instance: the 26 that exist, each for the frame
 // (kT = 0) and for a packed tile list (kT = kFTiles).  Written out, because a
 // generic flag-by-flag dispatch would instantiate combinations no frame runs.
 template <uint32_t kT>
-static bool launch_flags(uint32_t flags, const FrameArgs& a, size_t lds, hipStream_t st) {
+static bool launch_flags(uint32_t flags, const FrameArgs& a, const FramePlan& p, hipStream_t st) {
     switch (flags) {
 #define RT_INSTANCE(f) \
-    case (f): launch_instance<Frame<(f) | kT>>(a, lds, st); return true;
+    case (f): launch_instance<Frame<(f) | kT>>(a, p, st); return true;
 #define RT_INSTANCE_OCC(f) RT_INSTANCE(f) RT_INSTANCE((f) | kFOcc)
 #define RT_INSTANCE_OCC_BIN(f) RT_INSTANCE_OCC(f) RT_INSTANCE_OCC((f) | kFBin)
         // stats frames: they walk and count (7 waves per SIMD: the counters
@@ -662,52 +502,25 @@ static bool launch_flags(uint32_t flags, const FrameArgs& a, size_t lds, hipStre
     return false;
 }
 
-static SceneInstance instance_of(const FrameArgs& a, bool sort, bool have_occ, bool have_bins) {
-    return pick_scene_instance(a.variant, a.spp, a.accum != nullptr, a.count_work != 0u, sort, have_occ,
-                               have_bins, a.sc.tab_k, a.sc.stack_depth);
-}
-
-// Whether launch_scene runs this frame on a scene_kernel_w8 instance (the
-// ones that read bins).
-bool frame_reads_bins(const FrameArgs& a, bool sort) { return instance_of(a, sort, false, false).w8(); }
-
 // Variants compiled into this build (rt_create refuses the others).
 bool variant_available(uint32_t v) {
     return pick_scene_instance(v, 1, false, false, false, false, false, 0, 1).valid;
 }
 
-// sort: sorted rounds where they apply (the renderer's; off only under a test hook)
-hipError_t launch_scene(const FrameArgs& a_in, bool sort, hipStream_t st) {
+// p: the frame's plan (do_render made it; the frame's occluder lists and
+// bins, which the steps since filled in, finish its instance)
+hipError_t launch_scene(const FrameArgs& a_in, const FramePlan& p, hipStream_t st) {
     FrameArgs a = a_in;
-    // (bins: set only for a frame whose instance reads them, frame_reads_bins)
-    const SceneInstance inst = instance_of(a, sort, a.sc.prim_occ && a.sc.occ_sp && a.shadows,
-                                           a.bin_hdr && a.bin_ent && a.bin_info);
-    // wave mapping: spw samples x ppw pixels per wave (see rt_shade.h)
-    wave_tile_shape(a.spp, a.spw, a.g, a.ppw, a.tw, a.th);
-    a.rounds = (a.spp + a.spw - 1) / a.spw;
-    // wave-queue ticket size: adjacent wave tiles back to back on one wave
-    // reuse its CU's L1; a ticket of about four rounds of work balances that
-    // against the queue tail (C3, 1 round: 4 per ticket -4.1%; C5, 4 rounds:
-    // 1 per ticket, more is slower; profiles/r01/chunk_ab.log)
-    const uint32_t ck = (a.sc.opt >> kOptChunkShift) & 7u;
-    a.wq_chunk = ck ? 1u << (ck - 1u) : std::max(1u, 4u / std::max(1u, std::min(a.rounds, 4u)));
-    const size_t lds = FrameLds(inst.sorted, a.sc.tab_k, a.sc.stack_depth).bytes;
+    // (bins: set only for a frame whose instance reads them, bins_gate)
+    const SceneInstance inst =
+        p.inst.with(a.sc.prim_occ && a.sc.occ_sp && a.shadows, a.bin_hdr && a.bin_ent && a.bin_info);
+    a.spw = p.spw, a.g = p.g, a.ppw = p.ppw, a.rounds = p.rounds;
+    a.tw = p.grid.tw, a.th = p.grid.th;
+    a.wq_chunk = p.ticket;  // (the wave queue's launch may cap it)
     // (an instance outside the table: a bug in pick_scene_instance, a failed frame)
-    const bool known = inst.valid && (a.tiles ? launch_flags<kFTiles>(inst.flags(), a, lds, st)
-                                              : launch_flags<0u>(inst.flags(), a, lds, st));
+    const bool known = inst.valid && (a.tiles ? launch_flags<kFTiles>(inst.flags(), a, p, st)
+                                              : launch_flags<0u>(inst.flags(), a, p, st));
     return known ? hipGetLastError() : hipErrorInvalidDeviceFunction;
-}
-
-hipError_t launch_unpack(const uint32_t* packed, const uint32_t* tiles, uint32_t n_tiles,
-                         uint32_t ts, uint32_t tiles_x, uint32_t W, uint32_t H, uint32_t* img,
-                         hipStream_t st) {
-    const size_t total = (size_t)ts * ts * n_tiles;
-    const uint32_t blocks = static_cast<uint32_t>((total + kBlockThreads - 1) / kBlockThreads);
-    if (blocks) {
-        hipLaunchKernelGGL(unpack_kernel, dim3(blocks), dim3(kBlockThreads), 0, st, packed, tiles,
-                           n_tiles, ts, tiles_x, W, H, img);
-    }
-    return hipGetLastError();
 }
 
 }  // namespace rtamd

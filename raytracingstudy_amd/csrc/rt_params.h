@@ -10,7 +10,6 @@
 
 namespace rtamd {
 
-constexpr uint32_t kTileSide = 16;  // scene kernel: largest block tile (16x16 pixels per workgroup)
 constexpr uint32_t kMaxDepth = 16;  // octree depth limit (grid coordinates stay < 2^16, exact in f32)
 constexpr float kShadowEps = 1e-5f; // shadow-ray origin offset along the normal (world units)
 constexpr uint32_t kNoHit = 0xFFFFFFFFu;
@@ -19,17 +18,10 @@ constexpr uint32_t kNoHit = 0xFFFFFFFFu;
 // sphere past a leaf's end (rt_capi.cpp fills it)
 constexpr uint32_t kPrimPad = 4;
 
-// A/B toggles (rt_config.flags bits 20..27), results identical either way
+// A/B toggles (rt_config.flags bits 20..27), results identical either way;
+// bits 1..7 size a frame's launch: rt_sched.h (kOptBtsShift, kOptChunkShift, kOptNoWgCap)
 constexpr uint32_t kOptDeviceBuildRefuse = 1u << 0;  // bit 0: the device build reports running out
                                                      // of HBM (tests its host fallback)
-constexpr uint32_t kOptBtsShift = 1;       // bits 1..3: force the block-tile side (A/B):
-                                           // 0 auto, 1 = 16, 2 = 8, 3 = 4, 4 = 2 pixels
-constexpr uint32_t kOptNoWgCap = 1u << 7; // bit 7: 1-spp frames without the 3-workgroups-per-CU cap
-constexpr uint32_t kOptChunkShift = 4;     // bits 4..6: wave-queue tiles per ticket: 0 auto
-                                           // (4 / rounds, at least 1), k = 1..4 -> 1 << (k - 1);
-                                           // 5..7 are refused (a ticket must not span half
-                                           // a slot: the two-level queue's claim rule)
-constexpr uint32_t kOptChunkMax = 4;
 
 // Depth-K cell table (cell_table.hip): entry = {record.x, record.y (24 bits) |
 // depth << 24 | kind << 29} of the node covering each depth-K cell.

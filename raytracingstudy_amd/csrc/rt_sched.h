@@ -1,7 +1,9 @@
 // rt_sched.h — how a scene frame is scheduled, stated once: which kernel
-// instance runs it (SceneInstance, Frame<>), its wave-tile grid (WaveGrid) and
-// its workgroup's LDS layout (FrameLds).  Scalars only and no HIP types, so it
-// compiles with g++ too (tests/native/sched_dump.cpp); rt_params.h includes it.
+// instance runs it (SceneInstance, Frame<>), its wave-tile grid (WaveGrid), its
+// workgroup's LDS layout (FrameLds), all of these as the one plan the host
+// makes per frame (FramePlan), and how large the launch is (size_wave_queue,
+// size_block_tiles).  Scalars only and no HIP types, so it compiles with g++
+// too (tests/native/sched_dump.cpp); rt_params.h includes it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -15,6 +17,18 @@
 namespace rtamd {
 
 constexpr int kBlockThreads = 256;  // 4 waves of 64
+constexpr uint32_t kTileSide = 16;  // scene kernel: largest block tile (16x16 pixels per workgroup)
+
+// The A/B toggles that size a launch (rt_config.flags bits 21..27, SceneArgs::opt
+// bits 1..7; bit 0 is rt_params.h's), results identical either way
+constexpr uint32_t kOptBtsShift = 1;       // bits 1..3: force the block-tile side (A/B):
+                                           // 0 auto, 1 = 16, 2 = 8, 3 = 4, 4 = 2 pixels
+constexpr uint32_t kOptNoWgCap = 1u << 7; // bit 7: 1-spp frames without the 3-workgroups-per-CU cap
+constexpr uint32_t kOptChunkShift = 4;     // bits 4..6: wave-queue tiles per ticket: 0 auto
+                                           // (4 / rounds, at least 1), k = 1..4 -> 1 << (k - 1);
+                                           // 5..7 are refused (a ticket must not span half
+                                           // a slot: the two-level queue's claim rule)
+constexpr uint32_t kOptChunkMax = 4;
 
 // scene kernel variants (rt_config.flags bits 16..19, RT_FLAG_VARIANT_SHIFT);
 // 0 picks 13 for spp >= 8, else 4 (default_variant).  Numbers of the variants
@@ -118,6 +132,9 @@ struct WaveGrid {
     RT_HD uint32_t blocks() const { return grids * nbx * nby; }
     RT_HD uint32_t superblocks() const { return grids * nsx * nsy; }
     RT_HD uint32_t slot_shift() const { return wave_queue_slot_shift(superblocks(), blocks()); }
+    // words of one XCD's slot table: a slot per level-1 unit, the claim past
+    // the last one (kSlotNone) and the slot claimed half a slot early
+    RT_HD uint32_t slot_stride() const { return (slot_shift() == 12u ? superblocks() : blocks()) + 2u; }
 };
 
 // ---------------------------------------------------------------------------
@@ -160,6 +177,13 @@ struct SceneInstance {
     }
     RT_HD uint32_t min_waves() const { return waveq ? (stats ? 7u : 8u) : 1u; }
     RT_HD bool w8() const { return waveq && !stats; }  // scene_kernel_w8: the instances that read bins
+    // this instance once the frame's occluder lists and bins are known
+    RT_HD SceneInstance with(bool have_occ, bool have_bins) const {
+        SceneInstance s = *this;
+        s.occ = !stats && have_occ;
+        s.bin = !stats && waveq && have_bins;
+        return s;
+    }
 };
 
 // The instance of a frame.  count_work: a stats frame; sort_on: false only
@@ -188,9 +212,122 @@ RT_HD inline SceneInstance pick_scene_instance(uint32_t variant, uint32_t spp, b
         s.stats = true;  // block-tile queue, counting in every frame
     else if (variant != kVariantLaneUnified2NoStats)
         s.valid = false;
-    s.occ = !s.stats && have_occ;
-    s.bin = !s.stats && s.waveq && have_bins;
+    return s.with(have_occ, have_bins);
+}
+
+// ---------------------------------------------------------------------------
+// The plan of a scene frame, made once by the host (do_render)
+// ---------------------------------------------------------------------------
+
+struct FramePlan {
+    SceneInstance inst;  // before the occluder lists and the bins are known: inst.with()
+    WaveGrid grid;
+    // wave mapping: spw samples x ppw pixels per wave (see rt_shade.h), g =
+    // pow2ceil(spw) lanes per pixel, rounds of spw samples per pixel
+    uint32_t spw, g, ppw, rounds;
+    uint32_t slot_shift, slot_stride;  // the wave queue's slot size and per-XCD slot-table length
+    uint32_t lds_bytes;                // FrameLds of the instance
+    uint32_t ticket;                   // wave tiles per ticket, before the launch's cap (size_wave_queue)
+    bool ticket_forced;                // by kOptChunkShift: no cap
+};
+
+// n_tiles = 0: the frame; opt: SceneArgs::opt.
+RT_HD inline FramePlan plan_scene_frame(uint32_t variant, uint32_t spp, bool progressive, bool count_work,
+                                        bool sort_on, uint32_t tab_k, uint32_t stack_depth, uint32_t W,
+                                        uint32_t H, uint32_t n_tiles, uint32_t tile_size, uint32_t opt) {
+    FramePlan p = {pick_scene_instance(variant, spp, progressive, count_work, sort_on, false, false, tab_k,
+                                       stack_depth),
+                   WaveGrid(W, H, spp, n_tiles, tile_size)};
+    uint32_t tw, th;
+    wave_tile_shape(spp, p.spw, p.g, p.ppw, tw, th);
+    p.rounds = (spp + p.spw - 1) / p.spw;
+    p.slot_shift = p.grid.slot_shift();
+    p.slot_stride = p.grid.slot_stride();
+    p.lds_bytes = FrameLds(p.inst.sorted, tab_k, stack_depth).bytes;
+    // wave-queue ticket size: adjacent wave tiles back to back on one wave
+    // reuse its CU's L1; a ticket of about four rounds of work balances that
+    // against the queue tail (C3, 1 round: 4 per ticket -4.1%; C5, 4 rounds:
+    // 1 per ticket, more is slower; profiles/r01/chunk_ab.log)
+    const uint32_t ck = (opt >> kOptChunkShift) & 7u;
+    p.ticket = ck ? 1u << (ck - 1u) : 4u / (p.rounds < 1u ? 1u : p.rounds > 4u ? 4u : p.rounds);
+    p.ticket_forced = ck != 0u;
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// The size of a launch, from the plan and the device's occupancy numbers
+// (resident: workgroups of the kernel the device holds at its LDS size)
+// ---------------------------------------------------------------------------
+
+struct WaveQueueLaunch {
+    uint32_t grid, ticket;  // workgroups; wave tiles per ticket (FrameArgs::wq_chunk)
+};
+struct BlockTileLaunch {
+    uint32_t grid, side;  // workgroups; the block-tile side in pixels (FrameArgs::bts)
+};
+
+// Per-wave queue launch: grid = resident workgroups, capped by the work.
+// per_simd: the build's waves per SIMD (0: no cap); cus: the device's CUs.
+RT_HD inline WaveQueueLaunch size_wave_queue(uint64_t units, uint32_t resident, uint32_t cus, uint32_t per_simd,
+                                        uint32_t ticket, bool ticket_forced) {
+    // (the grid only sizes the launch; padding units of edge blocks are skipped)
+    const uint64_t want = (units + kBlockThreads / 64 - 1) / (kBlockThreads / 64);
+    // The occupancy query counts 8 workgroups per CU for the 7-wave builds
+    // (60-65 VGPRs), but their 94 SGPRs leave room for 7: the 8th per CU
+    // only starts when another exits, finds nothing and adds 8 queue atomics
+    // to the tail (profiles/r02/timeline_hwid.log).  Capped at the build's
+    // waves per SIMD: C3 -0.8%, 1/8 share -5% (profiles/r02/steal_ab.log,
+    // measured with the static per-XCD ranges that preceded the two-level queue)
+    const uint64_t cap = per_simd ? static_cast<uint64_t>(cus) * per_simd : resident;
+    uint64_t grid = resident < cap ? resident : cap;
+    if (want < grid) grid = want;
+    if (grid < 1u) grid = 1u;
+    WaveQueueLaunch s = {static_cast<uint32_t>(grid), ticket};
+    if (!ticket_forced) {
+        // auto ticket size, second half: a small launch (a multi-GPU share)
+        // has few units per wave, and big tickets lengthen its tail. N-way
+        // C3 shares: 4 per ticket best at 1/2 and 1/4, 2 at 1/8 (36 units a
+        // wave; profiles/r01/shard_chunk.log)
+        const uint64_t per_wave = units / (grid * (kBlockThreads / 64));
+        const uint32_t most = per_wave >= 64 ? 4u : per_wave >= 16 ? 2u : 1u;
+        if (most < s.ticket) s.ticket = most;
+    }
     return s;
+}
+
+// Block tiles in the frame (or in the packed tile list) for block-tile side b.
+RT_HD inline uint32_t count_block_tiles(uint32_t W, uint32_t H, uint32_t n_tiles, uint32_t tile_size,
+                                        uint32_t b) {
+    if (n_tiles) return n_tiles * (tile_size / b) * (tile_size / b);
+    return ((W + b - 1) / b) * ((H + b - 1) / b);
+}
+
+// Persistent launch: grid = resident workgroups; the block-tile side shrinks
+// (16 -> 8 -> 4 pixels, never below two wave tiles) until the tile queue holds
+// >= 8 tiles per resident workgroup, so the dynamic queue can even out costly
+// image regions to the end (A/B, profiles/r01/bts_ab.log: 1080p 64 spp picks
+// 8x8 tiles, -6.4% vs 16x16; a 1/4 or 1/8 multi-GPU share picks 4x4).
+// force: kOptBtsShift's field (0: auto; a side below two wave tiles is not forced).
+RT_HD inline BlockTileLaunch size_block_tiles(uint32_t W, uint32_t H, uint32_t n_tiles, uint32_t tile_size,
+                                              uint32_t tw, uint32_t th, uint32_t resident, uint32_t force) {
+    const uint32_t min_side = 2u * (tw > th ? tw : th);
+    uint32_t bts = kTileSide;
+    if (force && (kTileSide >> (force - 1u)) >= min_side)
+        bts = kTileSide >> (force - 1u);
+    else
+        while (bts / 2u >= min_side && count_block_tiles(W, H, n_tiles, tile_size, bts) < 8u * resident)
+            bts /= 2u;
+    const uint32_t tiles = count_block_tiles(W, H, n_tiles, tile_size, bts);
+    return {tiles < resident ? tiles : resident, bts};
+}
+
+// The block-tile queue's dynamic LDS.  1 spp: a wave's 64 lanes are 64
+// different pixels, whose walks thrash the L1 when 5 workgroups share a CU;
+// the dynamic LDS is padded so that at most 3 are resident (C2: 0.358 ->
+// 0.274 ms; 2 or 4 per CU slower, 4 spp unchanged; profiles/r01/c2_wg_cap_ab.log)
+constexpr uint32_t kOneSppLds = (160u * 1024u / 3u) & ~15u;  // 3 workgroups per CU
+RT_HD inline uint32_t block_tile_lds(uint32_t lds_bytes, uint32_t spw, uint32_t opt) {
+    return spw == 1u && !(opt & kOptNoWgCap) && lds_bytes < kOneSppLds ? kOneSppLds : lds_bytes;
 }
 
 }  // namespace rtamd

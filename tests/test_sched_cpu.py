@@ -1,9 +1,11 @@
 """How a scene frame is scheduled (csrc/rt_sched.h), on the CPU: which kernel
-instance runs it, its wave-tile grid and its workgroup's LDS layout.
+instance runs it, its wave-tile grid and its workgroup's LDS layout, the plan
+the host makes of all three per frame, and the size of the launch.
 tests/native/sched_dump.cpp, built with the address and undefined-behaviour
 sanitizers, prints the header's answers; the expected ones are written out
 here independently: the dispatch table of the round-13 issue, closed forms of
-the grid, and the LDS sizes as the launchers computed them before round 13.
+the grid, the LDS sizes as the launchers computed them before round 13, and
+the launch policy as the launchers held it before round 17.
 """
 import itertools
 import os
@@ -150,3 +152,130 @@ def test_frame_lds_layouts(dump, tab_k, depth):
     # sorted: no sums, the stackless walk's stacks, 4 per-wave regions
     assert srt[1] == srt[0] and srt[2] - srt[1] == _levels(tab_k, depth, True) * 256 * 8
     assert srt[3] - srt[2] == 4 * SORT_WAVE_BYTES and srt[4] == _sort_lds_bytes(tab_k, depth)
+
+
+# ---- the plan of a frame, and the size of its launch ----------------------------------
+# Expected values restate the launchers as they were before round 17, when
+# frame_counters, launch_scene, launch_waveq and launch_persistent each derived
+# their part: rt_kernels.hip and rt_frame.cpp of commit b82f6d6.
+
+CHUNK_SHIFT, BTS_SHIFT, NO_WG_CAP = 4, 1, 1 << 7                   # kOptChunkShift, kOptBtsShift, kOptNoWgCap
+ONE_SPP_LDS = (160 * 1024 // 3) & ~15                              # kOneSppLds
+
+
+def _plan_tail(spp, opt, grid, sorted_lds_bytes):
+    """What frame_counters and launch_scene derived: spw g ppw rounds slot_shift
+    slot_stride lds_bytes ticket ticket_forced (grid: the `grid` mode's row)."""
+    spw = min(spp, 64)
+    g = 1 << (spw - 1).bit_length()
+    rounds = _ceil(spp, spw)
+    blocks, sbs, shift = grid[8], grid[9], grid[11]
+    ck = (opt >> CHUNK_SHIFT) & 7
+    ticket = 1 << (ck - 1) if ck else max(1, 4 // max(1, min(rounds, 4)))
+    return (spw, g, 64 // g, rounds, shift, (sbs if shift == 12 else blocks) + 2, sorted_lds_bytes, ticket,
+            int(ck != 0))
+
+
+def _wave_queue(units, resident, cus, per_simd, ticket, forced):     # launch_waveq
+    want = _ceil(units, 4)
+    cap = cus * per_simd if per_simd else resident
+    grid = max(1, min(resident, cap, want))
+    if not forced:
+        per_wave = units // (grid * 4)
+        ticket = min(ticket, 4 if per_wave >= 64 else 2 if per_wave >= 16 else 1)
+    return grid, ticket
+
+
+def _block_tiles(w, h, n_tiles, ts, tw, th, resident, force):        # launch_persistent, count_block_tiles
+    count = lambda b: n_tiles * (ts // b) ** 2 if n_tiles else _ceil(w, b) * _ceil(h, b)
+    min_side, side = 2 * max(tw, th), 16
+    if force and (16 >> (force - 1)) >= min_side:
+        side = 16 >> (force - 1)
+    else:
+        while side // 2 >= min_side and count(side) < 8 * resident:
+            side //= 2
+    return side, min(count(side), resident)
+
+
+GEOMETRIES = [(1, 1, 0, 0), (7, 9, 0, 0), (64, 64, 0, 0), (130, 70, 0, 0), (1920, 1080, 0, 0),
+              (1920, 1080, 3, 64), (1920, 1080, 64, 64), (1920, 1080, 200, 128)]   # W H n_tiles tile_size
+OPTS = [0, 1 << CHUNK_SHIFT, 3 << CHUNK_SHIFT, 4 << CHUNK_SHIFT, 2 << BTS_SHIFT, NO_WG_CAP | 2 << CHUNK_SHIFT]
+# (variant, progressive, count_work, sort_on): cycled over the sweep, every one with every spp
+KINDS = [(0, 0, 0, 1), (0, 0, 1, 1), (0, 1, 0, 1), (LANE_UNIFIED_2, 0, 0, 1), (WAVEQ, 0, 0, 0),
+         (LANE_UNIFIED, 0, 0, 1), (0, 1, 1, 1)]
+
+
+def test_plan_is_what_the_five_places_derived(dump):
+    rows = []
+    for spp in range(1, 257):
+        for gi, geo in enumerate(GEOMETRIES):
+            for oi, opt in enumerate(OPTS):
+                i = spp + gi + oi
+                v, prog, count, sort_on = KINDS[i % len(KINDS)]
+                tab_k, depth = TREES[i % len(TREES)]
+                rows.append((v, spp, prog, count, sort_on, tab_k, depth, *geo, opt))
+    plans = dump("plan", rows)
+    picks = dump("pick", [(v, spp, prog, count, sort_on, 0, 0, tab_k, depth)
+                          for v, spp, prog, count, sort_on, tab_k, depth, *_ in rows])
+    grids = dump("grid", [(w, h, spp, n, ts) for _, spp, _, _, _, _, _, w, h, n, ts, _ in rows])
+    ldss = dump("lds", [(pick[4], row[5], row[6]) for row, pick in zip(rows, picks)])   # pick[4]: sorted
+    seen_sorted = seen_forced = seen_block_slots = 0
+    for row, plan, pick, grid, lds in zip(rows, plans, picks, grids, ldss):
+        assert plan[:10] == pick and plan[10:22] == grid, row
+        assert plan[22:] == _plan_tail(row[1], row[11], grid, lds[4]), row
+        seen_sorted += pick[4]
+        seen_forced += plan[30]
+        seen_block_slots += plan[26] == 6
+    assert seen_sorted and seen_forced and seen_block_slots
+
+
+def test_plan_known_answers(dump):
+    full, share = dump("plan", [(0, 64, 0, 0, 1, 0, 12, 1920, 1080, 0, 0, 0),
+                                (0, 64, 0, 0, 1, 0, 12, 1920, 1080, 64, 64, 0)])
+    # the full frame: 1x1 wave tile, 510 superblocks, superblock slots, 1 round, 4 wave tiles a ticket
+    assert full[10:12] == (1, 1) and full[19] == 510
+    assert full[25:28] == (1, 12, 512) and full[29:] == (4, 0)
+    # a 1/8 share of it as 64 packed 64x64 tiles: 64 superblocks, block slots
+    assert share[19] == 64 and share[26] == 6
+
+
+def test_wave_queue_launch_size(dump):
+    rows = [(units, res, cus, per_simd, ticket, forced)
+            for units in (1, 3, 4, 5, 63, 64, 255, 256, 4095, 4096, 32400, 262144, 524288, 2073600, 1 << 33)
+            for res, cus in ((1, 1), (8, 2), (1280, 256), (2048, 256), (2432, 304), (4, 256))
+            for per_simd in (0, 7, 8)
+            for ticket in (1, 2, 4)
+            for forced in (0, 1)]
+    for row, got in zip(rows, dump("waveq", rows)):
+        assert got == _wave_queue(*row), row
+    occ = (2048, 256, 8, 4, 0)      # resident, CUs, waves per SIMD, the plan's ticket, not forced
+    got = dump("waveq", [(2073600, *occ), (524288, *occ), (262144, *occ), (1, *occ), (262144, 2048, 256, 8, 4, 1)])
+    assert got[0] == (2048, 4)      # C3's frame
+    assert got[1][1] == 4           # a 1/4 share: 64 units a wave
+    assert got[2][1] == 2           # a 1/8 share: 32
+    assert got[3] == (1, 1)
+    assert got[4][1] == 4           # a forced ticket is not capped
+
+
+def test_block_tile_launch_size(dump):
+    rows = [(w, h, n, ts, tw, th, res, force)
+            for w, h, n, ts in GEOMETRIES + [(512, 513, 0, 0), (1920, 1080, 128, 64)]
+            for tw, th in ((1, 1), (2, 1), (2, 2), (4, 2), (4, 4), (8, 4), (8, 8))
+            for res in (1, 4, 256, 768, 1280, 2048)
+            for force in range(8)]
+    for row, got in zip(rows, dump("btiles", rows)):
+        assert got == _block_tiles(*row), row
+    got = dump("btiles", [(1920, 1080, 0, 0, 1, 1, 1280, 0), (1920, 1080, 64, 64, 1, 1, 1280, 0),
+                          (1920, 1080, 128, 64, 1, 1, 1280, 0), (1920, 1080, 0, 0, 8, 8, 1280, 0),
+                          (1920, 1080, 0, 0, 8, 8, 1280, 2)])
+    assert got[0] == (8, 1280)                  # 1080p at 64 spp
+    assert got[1][0] == 4 and got[2][0] == 4    # 1/8 and 1/4 shares
+    assert got[3][0] == 16 and got[4][0] == 16  # 1 spp: two 8x8 wave tiles a side, forced or not
+
+
+def test_block_tile_lds_caps_one_spp_at_three_workgroups(dump):
+    rows = [(lds, spw, opt) for lds in (0, 6144, 28672, ONE_SPP_LDS - 16, ONE_SPP_LDS, ONE_SPP_LDS + 16, 65536)
+            for spw in (1, 2, 4, 64) for opt in (0, NO_WG_CAP, 2 << BTS_SHIFT, NO_WG_CAP | 1 << CHUNK_SHIFT)]
+    for (lds, spw, opt), got in zip(rows, dump("btlds", rows)):
+        assert got == (max(lds, ONE_SPP_LDS) if spw == 1 and not opt & NO_WG_CAP else lds,), (lds, spw, opt)
+    assert 3 * ONE_SPP_LDS <= 160 * 1024 < 4 * ONE_SPP_LDS and ONE_SPP_LDS % 16 == 0

@@ -4,8 +4,8 @@ kernels' machine code unchanged (comments, diagnostic-only code).
 
     python tools/restamp_pmc.py <git-rev the summary was profiled at> [names.json]
 
-Compiles the frame kernels (rt_kernels.hip, and rt_records.hip where the tree
-has it) to gfx950 assembly at <rev> and in the working tree (the Makefile's
+Compiles the frame kernels (rt_kernels.hip, and rt_compat.hip and
+rt_records.hip where the tree has them) to gfx950 assembly at <rev> and in the working tree (the Makefile's
 device flags) and restamps every entry with this tree's kernel_source_id only
 if tools/isa_diff.py finds every kernel identical (names.json: its table of
 renamed kernels).  Records the old stamp and the reason.
@@ -28,7 +28,7 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx9
 
 def isa(src_dir: str) -> str:
     text = []
-    for unit in ("rt_kernels", "rt_records"):
+    for unit in ("rt_kernels", "rt_compat", "rt_records"):
         if os.path.exists(os.path.join(src_dir, unit + ".hip")):
             out = os.path.join(src_dir, unit + ".restamp.s")
             subprocess.check_call(["/opt/rocm/bin/hipcc", *FLAGS, unit + ".hip", "-o", out], cwd=src_dir,
