@@ -21,6 +21,8 @@ import raytracingstudy_amd as rt
 from raytracingstudy_amd import _lib
 from raytracingstudy_amd.camera import scene_pose, translation_pose
 
+import gbuffer_ref
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,35 +85,8 @@ def _expected(name, w, h, pose="scene", custom_k=False):
     """The oracle's G-buffer: t (h, w) f32, sphere (h, w) u32, normal (h, w, 4) f32,
     albedo (h, w) u32, and the summed node / prim counters."""
     import oracle
-    sc = _oracle_scene(name)
     sp, al = _spheres(name)
-    P, K = POSES[pose](), _intrinsic(w, h, custom_k)
-    o = P[3, :3].astype(np.float32)
-    t = np.full((h, w), np.inf, np.float32)
-    sphere = np.full((h, w), NO_HIT, np.uint32)
-    d = np.zeros((h, w, 3), np.float32)
-    nodes = prims = 0
-    for y in range(h):
-        for x in range(w):
-            d[y, x] = oracle.get_ray(P, K, float(x), float(y))
-            hit, th, idx, cnt = sc.trace(o, d[y, x])
-            if hit:
-                t[y, x], sphere[y, x] = th, idx
-            nodes += int(cnt[2])
-            prims += int(cnt[3])
-    hit = sphere != NO_HIT
-    normal = np.zeros((h, w, 4), np.float32)
-    rec = sp[sphere[hit]]
-    p = o[None, :] + t[hit][:, None] * d[hit]           # float32 throughout: one rounding per operation
-    ir = np.float32(1.0) / rec[:, 3]
-    normal[hit, :3] = (p - rec[:, :3]) * ir[:, None]
-    albedo = np.zeros((h, w), np.uint32)
-    albedo[hit] = al[sphere[hit]]
-    out = dict(t=t, sphere=sphere, normal=normal, albedo=albedo, nodes=nodes, prims=prims, dirs=d)
-    for a in out.values():
-        if isinstance(a, np.ndarray):
-            a.setflags(write=False)
-    return out
+    return gbuffer_ref.expected(oracle, _oracle_scene(name), sp, al, POSES[pose](), _intrinsic(w, h, custom_k), w, h)
 
 
 def _renderer(name, w, h, pose="scene", custom_k=False, albedo=True, **kw):
