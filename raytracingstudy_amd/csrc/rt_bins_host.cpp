@@ -50,9 +50,9 @@ int bins_buffers(rt_renderer* r, const FrameArgs& a, uint32_t nb, hipStream_t st
         if ((ost = ensure(r, s.ent, 2 * want))) return ost;
     }
     if ((ost = ensure(r, s.rects, std::max(1u, r->n_spheres))) ||
-        (ost = ensure(r, s.cnt, 2ull * nb + 1ull)) || (ost = ensure(r, s.offs, nb + 1ull)) ||
+        (ost = ensure(r, s.cnt, bin_zeroed_words(nb))) || (ost = ensure(r, s.offs, nb + 1ull)) ||
         (ost = ensure(r, s.hdr, size_t(nb) * (1u + kBinCap))) ||  // (and the tile words)
-        (ost = ensure(r, s.wide, 2ull * kBinWideCap)) || (ost = ensure(r, s.info, kBinInfoWords)))
+        (ost = ensure(r, s.wide, 2ull * kBinWideCap)))
         return ost;
     if (s.temp_items < nb + 1u || !s.temp.p) {
         const size_t bytes = bins_scan_temp_bytes(nb + 1u);
@@ -88,13 +88,14 @@ BinBuild bins_build_args(const rt_renderer* r, const FrameArgs& a, const FramePl
     b.frame_id = a.frame_id;
     b.rects = s.rects.p;
     b.counts = s.cnt.p;
-    b.cursor = s.cnt.p + nb + 1u;
+    b.cursor = s.cnt.p + bin_cursor_at(nb);
+    b.decide = s.cnt.p + bin_decide_at(nb);
+    b.info = s.cnt.p + bin_info_at(nb);
     b.offs = s.offs.p;
     b.hdr = s.hdr.p;
     b.ent = s.ent.p;
     b.tiles = reinterpret_cast<unsigned long long*>(s.hdr.p + nb);
     b.wide = s.wide.p;
-    b.info = s.info.p;
     b.mirror = s.mirror_dev;
     b.temp = s.temp.p;
     b.temp_bytes = s.temp.n;
@@ -123,7 +124,7 @@ int bins_launch(rt_renderer* r, FrameArgs& a, const BinBuild& b, hipStream_t st)
     a.bin_ent = s.ent.p;
     a.bin_nb = b.nbx * b.nby;
     a.bin_wide = s.wide.p;
-    a.bin_info = s.info.p;
+    a.bin_info = b.info;
     a.bin_nbx = b.nbx;
     return RT_OK;
 }

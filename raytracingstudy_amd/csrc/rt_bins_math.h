@@ -187,6 +187,24 @@ RT_BINS_HD inline uint64_t bin_tile_word(const uint32_t* rects, uint32_t cnt, ui
     return w;
 }
 
+// ---- the frame's constants as one word ----
+// What every wave tile of a frame needs of the build beside its own bin: the
+// fallback flag (as one bit), the wide list's length (<= kBinWideCap) and the
+// logarithms of the wave tile's sides (<= kBinShift).  The frame kernel reads
+// them once per wave and carries them in one scalar register:
+// bit 0 flag != 0, bits 1-6 the wide count, bits 7-8 ltw, bits 9-10 lth.
+RT_BINS_HD inline bool bin_consts_fit(uint32_t wide, uint32_t ltw, uint32_t lth) {
+    return wide <= kBinWideCap && ltw <= kBinShift && lth <= kBinShift;
+}
+// (of values that fit; the flag word is any value)
+RT_BINS_HD inline uint32_t bin_consts_pack(uint32_t flag, uint32_t wide, uint32_t ltw, uint32_t lth) {
+    return (flag ? 1u : 0u) | (wide << 1) | (ltw << 7) | (lth << 9);
+}
+RT_BINS_HD inline bool bin_consts_flag(uint32_t c) { return (c & 1u) != 0u; }
+RT_BINS_HD inline uint32_t bin_consts_wide(uint32_t c) { return (c >> 1) & 63u; }
+RT_BINS_HD inline uint32_t bin_consts_ltw(uint32_t c) { return (c >> 7) & 3u; }
+RT_BINS_HD inline uint32_t bin_consts_lth(uint32_t c) { return (c >> 9) & 3u; }
+
 // ---- the host's policy (rt_bins_host.cpp screen_bins) ----
 // What a frame's build reports: the bin_info words on the device, mirrored to
 // the renderer's pinned copy, which the next frames read without a sync.
@@ -200,6 +218,16 @@ enum BinInfoWord : uint32_t {
     kBinInfoFrame,      // the frame id the words belong to
     kBinInfoWords = 8
 };
+// The build's zeroed words are one allocation, cleared by one memset: the
+// bins' counts [nb + 1] (the scan's last item is 0), their fill cursors [nb],
+// the decide kernel's partial results and arrival counter (round 19), the info
+// words.
+enum BinDecideWord : uint32_t { kBinDecNonEmpty = 0, kBinDecLongest, kBinDecOver, kBinDecArrived, kBinDecWords };
+inline size_t bin_cursor_at(uint32_t nb) { return size_t(nb) + 1u; }
+inline size_t bin_decide_at(uint32_t nb) { return 2u * size_t(nb) + 1u; }
+inline size_t bin_info_at(uint32_t nb) { return bin_decide_at(nb) + kBinDecWords; }
+inline size_t bin_zeroed_words(uint32_t nb) { return bin_info_at(nb) + kBinInfoWords; }
+
 constexpr uint32_t kBinFlagCapacity = 1u;  // the entries do not fit the buffer
 constexpr uint32_t kBinFlagWide = 2u;      // the wide list overflowed
 constexpr uint32_t kBinFlagDense = 4u;     // mean list length over kBinMeanMax

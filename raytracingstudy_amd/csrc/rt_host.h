@@ -79,15 +79,16 @@ struct BinBuild {
     uint32_t mean_max;          // the frame walks over this mean list length
     uint32_t frame_id;
     uint4* rects;               // [n_spheres] scratch
-    uint32_t* counts;           // [nbx * nby + 1], then
-    uint32_t* cursor;           // [nbx * nby] in the same allocation
+    uint32_t* counts;           // [nbx * nby + 1], then in the same allocation (rt_bins_math.h):
+    uint32_t* cursor;           // [nbx * nby],
+    uint32_t* decide;           // [kBinDecWords] bins_decide's partial results and arrival counter,
+    uint32_t* info;             // [kBinInfoWords]
     uint32_t* offs;             // [nbx * nby + 1]
     uint2* hdr;                 // [nbx * nby], the tile words behind them (FrameArgs::bin_nb)
     uint4* ent;                 // [2 * capacity]
     unsigned long long* tiles;  // [nbx * nby * tiles per bin] tile words (rt_bins_math.h)
     uint4* wide;               // [2 * kBinWideCap]
-    uint32_t* info;             // [kBinInfoWords]
-    uint32_t* mirror;           // the renderer's pinned copy of info (device pointer)
+    uint32_t* mirror;          // the renderer's pinned copy of info (device pointer)
     void* temp;                 // the scan's scratch
     size_t temp_bytes;
 };
@@ -210,8 +211,7 @@ struct MultiState {
 struct ScreenBinState {
     DerivedRecords<uint32_t> first_ref;  // per sphere, made once per scene
     DevBuf<uint4> rects, ent, wide;
-    DevBuf<uint32_t> cnt, offs, info;    // cnt: counts and cursors; info: the frame's info words
-    // the bins' headers, then the tile words in the same allocation: 64 per
+    DevBuf<uint32_t> cnt, offs;  // cnt: counts, cursors, bins_decide's words, the frame's info words    // the bins' headers, then the tile words in the same allocation: 64 per
     // bin whatever the frame's wave tile (8 B a pixel, 16.6 MB at 1080p), so a
     // change of spp between frames reallocates nothing
     DevBuf<uint2> hdr;
@@ -239,7 +239,6 @@ struct ScreenBinState {
         wide.release();
         cnt.release();
         offs.release();
-        info.release();
         hdr.release();
         temp.release();
         if (e0) (void)hipEventDestroy(e0);

@@ -100,6 +100,14 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
     // wait) on every staged leaf.  C5 -1.2%, C5d -0.3% (sorted), C3 -0.4%
     // (profiles/r06/ab_leaf_base_*.log)
     const uint32_t lbs = __builtin_amdgcn_readfirstlane(leaf_buf_base(a.sc, kSort));
+    // what every pixel of the frame needs of its bins beside its own bin (the
+    // fallback flag, the wide list's length, the logarithms of the wave tile's
+    // sides), read once per wave into one SGPR (round 19): each pixel read
+    // them again through bin_info, two scalar waits at the head of its chain
+    // and two dependent loads behind its entries
+    uint32_t binc = 0;
+    if constexpr (C::bin && !kSort)
+        binc = bin_frame_consts(static_cast<uint32_t>(__builtin_ctz(a.tw)), static_cast<uint32_t>(__builtin_ctz(a.th)));
     // the next frame's counters, queue heads and slot table (the other set,
     // FrameArgs::ctr_next): zeroed here by the first workgroup, so frames run
     // back to back with no memset launch between them.  The previous frame,
@@ -283,7 +291,7 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
                                           n_prims, bs);
                 else
                     shade_wave_tile<C>(a, acc, stk, ox, oy, obase, n_primary, n_shadow, n_nodes,
-                                       n_prims, bs, lbs);
+                                       n_prims, bs, lbs, binc);
 #ifdef RT_TIMELINE
                 // per unit {start, end, hw_id << 32 | xcc << 16 | wave index}
                 // after the 65536 per-wave records

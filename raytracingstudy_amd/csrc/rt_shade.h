@@ -71,7 +71,8 @@ __device__ __forceinline__ uint32_t pack_rgba8(const PixelOut& p) {
 // kBin: the primary ray is answered from the frame's screen-space bins
 // (rt_bins.h; (tox, toy): the wave tile's origin pixel, wave-uniform); a tile
 // whose bin is over the cap, or a frame whose builder raised its flag, walks
-// under a wave-uniform branch.
+// under a wave-uniform branch.  binc: the frame's constants of the bins
+// (bin_frame_consts, read once per wave).
 // C: the frame's switches (Frame<>, rt_sched.h).
 template <class C>
 __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uint32_t x,
@@ -79,7 +80,8 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                                                          bool valid, uint32_t& n_shadow,
                                                          uint32_t& n_nodes, uint32_t& n_prims,
                                                          void* stk, uint32_t* bs, uint32_t lbs,
-                                                         uint32_t tox = 0, uint32_t toy = 0) {
+                                                         uint32_t tox = 0, uint32_t toy = 0,
+                                                         uint32_t binc = 0) {
     constexpr bool kStats = C::stats, kCam8 = C::cam8, kOcc = C::occ, kBin = C::bin;
     const SceneArgs& S = a.sc;
     KernArgs* ka = kernargs();
@@ -112,10 +114,8 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
         if (kBin && phase == 0) {
             uint2 bh;
             unsigned long long bw;
-            // (the wave tile's sides are powers of two: wave_tile_shape)
-            binned = !bin_header(tox, toy, static_cast<uint32_t>(__builtin_ctz(kernargs()->tw)),
-                                 static_cast<uint32_t>(__builtin_ctz(kernargs()->th)), bh, bw);
-            if (binned) hit = bin_nearest(bh, bw, active, r0, r1, r2, d0, d1, d2, t, idx);
+            binned = !bin_header(tox, toy, binc, bh, bw);
+            if (binned) hit = bin_nearest(bh, bw, active, r0, r1, r2, d0, d1, d2, t, idx, binc);
         }
         if (active && !binned) {
             RT_BS(kBsPhase);
@@ -145,6 +145,12 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                 RT_BS(kBsShadeLoad);  // the sphere record
                 RT_BS(kBsShadeLoad);  // the albedo
                 const float4 sp = kb->sc.prim_sp[idx];
+                // the albedo and the occluder header depend on idx alone:
+                // requested with the sphere, in front of one wait (round 19).
+                // A lane facing away from the light loads a header it ignores
+                // (prim_occ holds one for every reference).
+                al = kb->sc.prim_al[idx];
+                if (kOcc) occ_hdr = kb->sc.prim_occ[idx];
                 const float p0 = r0 + t * d0;
                 const float p1 = r1 + t * d1;
                 const float p2 = r2 + t * d2;
@@ -155,8 +161,6 @@ __device__ __forceinline__ PixelOut sample_color_unified(const FrameArgs& a, uin
                 const float ndl = n0 * kb->L[0] + n1 * kb->L[1] + n2 * kb->L[2];
                 lam = ndl > 0.0f ? ndl : 0.0f;
                 want_shadow = ndl > 0.0f && kb->shadows;
-                al = kb->sc.prim_al[idx];
-                if (kOcc && want_shadow) occ_hdr = kb->sc.prim_occ[idx];
                 r0 = p0 + n0 * kShadowEps;
                 r1 = p1 + n1 * kShadowEps;
                 r2 = p2 + n2 * kShadowEps;
@@ -193,7 +197,8 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
                                                 uint32_t ox, uint32_t oy, uint32_t obase,
                                                 uint32_t& n_primary,
                                                 uint32_t& n_shadow, uint32_t& n_nodes,
-                                                uint32_t& n_prims, uint32_t* bs, uint32_t lbs) {
+                                                uint32_t& n_prims, uint32_t* bs, uint32_t lbs,
+                                                uint32_t binc = 0) {
     constexpr bool kTiles = C::tiles, kProg = C::prog;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t spw = a.spw, g = a.g;
@@ -217,10 +222,13 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
         const bool valid = lane_ok && sg < s_end;
         n_primary += static_cast<uint32_t>(__popcll(__ballot(valid)));  // wave-uniform
         PixelOut c = sample_color_unified<C>(a, x, y, hp, sg, valid, n_shadow, n_nodes, n_prims, stk,
-                                             bs, lbs, ox, oy);
+                                             bs, lbs, ox, oy, binc);
         // Pixel sum of this round: pairwise butterfly over the pixel's g
         // lanes (missing samples are 0) = oracle.c:tree_sum; rounds are then
         // added in order in the leader's LDS slot.
+        // (Round 19, neither kept: the steps up to m = 8 as DPP operands and 16,
+        // 32 as row and half swaps, no LDS round trip, C3 +1.5%; the leader's
+        // slot not written and read back in a frame of one round, C3 +0.5%.)
         if (!valid) c = PixelOut{0.0f, 0.0f, 0.0f};
         for (uint32_t m = 1; m < g; m <<= 1) {
             c.r += __shfl_xor(c.r, static_cast<int>(m), 64);

@@ -146,11 +146,12 @@ __device__ __forceinline__ void shade_pixel_sorted(const FrameArgs& a, float* wl
         if (kBin) {  // (x, y) is the wave's one pixel: a 1x1 tile of its bin
             uint2 bh;
             unsigned long long bw;
-            binned = !bin_header(x, y, 0u, 0u, bh, bw);
+            const uint32_t bc = bin_frame_consts(0u, 0u);
+            binned = !bin_header(x, y, bc, bh, bw);
             if (binned) {
                 KernArgs* kc = kernargs();
                 hit = bin_nearest(bh, bw, valid, kc->cam.o[0], kc->cam.o[1], kc->cam.o[2], d0, d1, d2, t,
-                                  idx);
+                                  idx, bc);
             }
         }
         if (valid && !binned) {

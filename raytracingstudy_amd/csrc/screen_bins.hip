@@ -5,12 +5,13 @@
 //
 // Queued on the frame's stream before the frame kernel, every plain frame (the
 // camera moves every frame in the Displayer), with no host synchronisation:
-//   memset            the bins' counts and cursors, the info words
+//   memset            the bins' counts and cursors, bins_decide's words, the
+//                     info words (one allocation, one memset)
 //   bins_count        per sphere: its class and rectangle (rt_bins_math.h,
 //                     f64), one atomic per bin it overlaps; wide spheres
 //                     join the frame-level list
 //   exclusive scan    counts -> each bin's first entry (hipCUB)
-//   bins_decide       one block: totals, the frame's fallback flag (entries
+//   bins_decide       a bin a thread: totals, the frame's fallback flag (entries
 //                     over the buffer, wide list overflowed, lists too long on
 //                     average), mirrored into the renderer's pinned words
 //   bins_fill         per sphere: its entry into every bin it overlaps
@@ -84,39 +85,60 @@ __global__ void __launch_bounds__(kBlockThreads)
     }
 }
 
-// One block.  offs[nb] = the total (the scan ran over nb + 1 counts, the last 0).
+// A bin a thread (round 19; one block of 256 threads walked 127 bins each with
+// dependent loads, 20 us of latency on the frame's stream at 1080p).  A block
+// reduces its bins to {non-empty, longest, over the cap} and adds them to the
+// `dec` words (zeroed by the build's memset) with device-scope atomics; the
+// block that arrives last, by the counter among them, reads the sums and
+// writes the frame's words.  Nobody waits for another block; the sums are of
+// integers, so two builds of one frame give the same words.
+// offs[nb] = the total (the scan ran over nb + 1 counts, the last 0).
 __global__ void __launch_bounds__(kBlockThreads)
     bins_decide_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs, uint32_t nb,
                        uint32_t capacity, uint32_t cap, uint32_t mean_max, uint32_t frame_id,
-                       uint32_t* __restrict__ info, uint32_t* __restrict__ mirror) {
-    __shared__ uint32_t s_ne[kBlockThreads], s_mx[kBlockThreads], s_ov[kBlockThreads];
-    uint32_t ne = 0, mx = 0, ov = 0;
-    for (uint32_t b = threadIdx.x; b < nb; b += kBlockThreads) {
-        const uint32_t c = counts[b];
-        ne += c ? 1u : 0u;
-        mx = max(mx, c);
-        ov += c > cap ? 1u : 0u;
+                       uint32_t* __restrict__ dec, uint32_t* __restrict__ info,
+                       uint32_t* __restrict__ mirror) {
+    constexpr uint32_t kWaves = kBlockThreads / 64u;
+    __shared__ uint32_t s_ne[kWaves], s_mx[kWaves], s_ov[kWaves];
+    const uint32_t b = blockIdx.x * kBlockThreads + threadIdx.x;
+    const uint32_t c = b < nb ? counts[b] : 0u;
+    uint32_t ne = c ? 1u : 0u, mx = c, ov = c > cap ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ne += __shfl_xor(ne, off, 64);
+        mx = max(mx, static_cast<uint32_t>(__shfl_xor(mx, off, 64)));
+        ov += __shfl_xor(ov, off, 64);
     }
-    s_ne[threadIdx.x] = ne;
-    s_mx[threadIdx.x] = mx;
-    s_ov[threadIdx.x] = ov;
+    if ((threadIdx.x & 63u) == 0u) {
+        s_ne[threadIdx.x >> 6] = ne;
+        s_mx[threadIdx.x >> 6] = mx;
+        s_ov[threadIdx.x >> 6] = ov;
+    }
     __syncthreads();
-    for (uint32_t d = kBlockThreads / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) {
-            s_ne[threadIdx.x] += s_ne[threadIdx.x + d];
-            s_mx[threadIdx.x] = max(s_mx[threadIdx.x], s_mx[threadIdx.x + d]);
-            s_ov[threadIdx.x] += s_ov[threadIdx.x + d];
-        }
-        __syncthreads();
-    }
     if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < kWaves; ++w) {
+            ne += s_ne[w];
+            mx = max(mx, s_mx[w]);
+            ov += s_ov[w];
+        }
+        if (ne) atomicAdd(dec + kBinDecNonEmpty, ne);
+        if (mx) atomicMax(dec + kBinDecLongest, mx);
+        if (ov) atomicAdd(dec + kBinDecOver, ov);
+        // (release: this block's adds before its arrival; acquire: every
+        // block's adds before the last one's reads)
+        __threadfence();
+        if (atomicAdd(dec + kBinDecArrived, 1u) != gridDim.x - 1u) return;
+        __threadfence();
+        ne = __hip_atomic_load(dec + kBinDecNonEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        mx = __hip_atomic_load(dec + kBinDecLongest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ov = __hip_atomic_load(dec + kBinDecOver, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t total = offs[nb], nw = info[kBinInfoWide];
         uint32_t flag = 0u;
         if (total > capacity) flag |= kBinFlagCapacity;
         if (nw > kBinWideCap) flag |= kBinFlagWide;
-        if (static_cast<unsigned long long>(total) > static_cast<unsigned long long>(mean_max) * s_ne[0])
+        if (static_cast<unsigned long long>(total) > static_cast<unsigned long long>(mean_max) * ne)
             flag |= kBinFlagDense;
-        const uint32_t w[kBinInfoWords] = {flag, nw, total, s_ne[0], s_mx[0], s_ov[0], frame_id, 0u};
+        const uint32_t w[kBinInfoWords] = {flag, nw, total, ne, mx, ov, frame_id, 0u};
         for (uint32_t k = 0; k < kBinInfoWords; ++k) {
             info[k] = w[k];
             // the renderer's pinned copy (plain system-scope stores, the frame id last)
@@ -222,9 +244,8 @@ size_t bins_scan_temp_bytes(uint32_t n_items) {
 hipError_t launch_screen_bins(const BinBuild& b, hipStream_t st) {
     const uint32_t nb = b.nbx * b.nby;
     hipError_t e;
-    // counts[nb + 1] and cursor[nb] are one allocation (b.counts, then b.cursor)
-    if ((e = hipMemsetAsync(b.counts, 0, (2ull * nb + 1ull) * sizeof(uint32_t), st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(b.info, 0, kBinInfoWords * sizeof(uint32_t), st)) != hipSuccess) return e;
+    // counts[nb + 1], cursor[nb], bins_decide's words and the info words are one allocation
+    if ((e = hipMemsetAsync(b.counts, 0, bin_zeroed_words(nb) * sizeof(uint32_t), st)) != hipSuccess) return e;
     BinCam cam;
     memcpy(cam.K, b.K, sizeof(cam.K));
     memcpy(cam.R, b.R, sizeof(cam.R));
@@ -236,8 +257,9 @@ hipError_t launch_screen_bins(const BinBuild& b, hipStream_t st) {
     size_t bytes = b.temp_bytes;
     if ((e = hipcub::DeviceScan::ExclusiveSum(b.temp, bytes, b.counts, b.offs, nb + 1u, st)) != hipSuccess)
         return e;
-    hipLaunchKernelGGL(bins_decide_kernel, dim3(1), dim3(kBlockThreads), 0, st, b.counts, b.offs, nb,
-                       b.capacity, b.cap, b.mean_max, b.frame_id, b.info, b.mirror);
+    hipLaunchKernelGGL(bins_decide_kernel, dim3((nb + kBlockThreads - 1) / kBlockThreads), dim3(kBlockThreads),
+                       0, st, b.counts, b.offs, nb, b.capacity, b.cap, b.mean_max, b.frame_id, b.decide,
+                       b.info, b.mirror);
     if (b.n_spheres)
         hipLaunchKernelGGL(bins_fill_kernel, dim3(ns), dim3(kBlockThreads), 0, st, b.spheres, b.first_ref,
                            b.n_spheres, b.rects, b.offs, b.cursor, b.info, b.nbx, b.capacity, b.ent);
