@@ -42,6 +42,8 @@
  *     src/renderer.cu:57-82)
  *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
  *     the octree which spheres touch a ball)
+ *   (none: as above; nothing asks which spheres are       rt_query_closest / rt_closest_at
+ *     nearest to a point)
  *   (none: no error reporting, all void)                  rt_last_error
  *
  * Threading: one handle per host thread / stream; calls on one handle are not
@@ -505,6 +507,62 @@ int rt_query_overlaps(rt_renderer* r, const void* dev_probes, uint32_t n, uint32
  * (INTEGRATION.md). */
 int rt_overlaps_at(rt_renderer* r, const float center[3], float radius, uint32_t k,
                    uint32_t* indices_out, uint32_t* count_out);
+
+/* ---- closest-sphere queries ------------------------------------------------ */
+/* Which scene spheres are nearest to this point, and how far away their
+ * surfaces are: a click that missed (rt_pick returned RT_NO_HIT) snapping to
+ * the nearest sphere, clearances before there is contact, each sphere's k
+ * nearest neighbours, the distance to the nearest surface at many points.  The
+ * reference has no counterpart (Octree::traverse is a stub,
+ * include/octree.h:19-21).
+ * A query is an rt_probe: `center` is the point p, `radius` the search radius
+ * R, the largest surface distance of interest.  For scene sphere (c, r):
+ * dx = p.x - c.x (likewise dy, dz), d2 = (dx*dx + dy*dy) + dz*dz, key =
+ * sqrtf(d2) - r: all f32, in that order, no contraction, sqrtf correctly
+ * rounded.  key is the signed distance from p to the sphere's surface,
+ * negative inside the sphere.  The accepted set is every scene sphere with
+ * key <= R (closed).  R = +inf is allowed: the unbounded nearest neighbour.
+ * R = -0 is 0.  A probe with a non-finite centre component, a NaN R or R < 0
+ * has an empty set.  Each sphere counts once, however many octree leaves list
+ * it.  This is not rt_query_overlaps' set: its d2 <= (R + r)^2 rounds
+ * differently, so a sphere at the very edge may be in one and not the other.
+ * The answer is the k smallest members by (key ascending, then sphere index
+ * ascending), 1 <= k <= RT_CLOSEST_MAX.
+ *   dev_probes  n rt_probe in device memory.
+ *   dev_near    n*k rt_near, probe-major: probe i's slots [i*k, i*k + k) hold
+ *               its answer in that order; slots past the probe's count hold
+ *               {the probe's radius as given, RT_NO_HIT} (multi-hit's tmax
+ *               convention).  Every slot is written.
+ *   dev_counts  n uint32 or NULL: min(k, size of the set).  There is no "more"
+ *               bit: the search stops looking beyond the k-th distance, and
+ *               with it gives up knowing whether the set is larger.
+ * flags: RT_CLOSEST_SKIP_SELF leaves sphere index i out of probe i's set (a
+ * probe with i >= n_spheres skips nothing): the scene's own device sphere list
+ * as the probes with this flag is "each sphere's k nearest neighbours" (the
+ * fourth component is then the search radius).
+ * stream, ordering, stats and error codes as rt_query_overlaps: asynchronous
+ * unless stats != NULL, ordered after the handle's earlier work; primary_rays
+ * = shadow_rays = 0, nodes_visited = node records the query read,
+ * prims_tested = key evaluations, ms = device time of the launch.  k == 0,
+ * k > RT_CLOSEST_MAX, unknown flag bits, or a NULL dev_probes / dev_near with
+ * n > 0: RT_E_INVALID.  n == 0: RT_OK, nothing launched.  No scene:
+ * RT_E_NOSCENE.  Reads scene state only: it never changes a frame; a
+ * multi-device handle answers from devices[0]. */
+typedef struct rt_near {
+    float dist;      /* the key: signed distance to the sphere's surface          */
+    uint32_t sphere; /* index into the caller's sphere list; a free slot: RT_NO_HIT */
+} rt_near; /* 8 bytes */
+#define RT_CLOSEST_MAX 16
+enum { RT_CLOSEST_SKIP_SELF = 1u }; /* probe i leaves sphere index i out */
+int rt_query_closest(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_t k, uint32_t flags,
+                     void* dev_near, void* dev_counts, void* stream, rt_stats* stats);
+/* A one-probe query that waits for the answer, like rt_overlaps_at.  near_out
+ * has room for k rt_near, filled as dev_near above (free slots hold max_dist);
+ * count_out (may be NULL) as dev_counts.  A point along rt_pick's ray, or the
+ * camera's focus, goes here to snap a missed click to the nearest sphere
+ * (INTEGRATION.md). */
+int rt_closest_at(rt_renderer* r, const float point[3], float max_dist, uint32_t k,
+                  rt_near* near_out, uint32_t* count_out);
 
 /* ---- first-hit G-buffer --------------------------------------------------- */
 /* The per-pixel geometry of the frame the current size and camera would

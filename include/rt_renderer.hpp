@@ -195,6 +195,23 @@ public:
         if (more) *more = (count & RT_OVERLAP_MORE) != 0;
         return count & ~RT_OVERLAP_MORE;
     }
+    // the k scene spheres nearest each probe point within its search radius, by
+    // (signed surface distance, sphere index) (rt_query_closest): n rt_probe ->
+    // n*k rt_near, probe-major, and n uint32 counts (or null), all in device
+    // memory; 1 <= k <= RT_CLOSEST_MAX; flags RT_CLOSEST_SKIP_SELF
+    void queryClosest(const void* dev_probes, uint32_t n, uint32_t k, void* dev_near,
+                      void* dev_counts = nullptr, uint32_t flags = 0, void* stream = nullptr,
+                      rt_stats* stats = nullptr) {
+        check(rt_query_closest(r_, dev_probes, n, k, flags, dev_near, dev_counts, stream, stats), r_);
+    }
+    // the k spheres nearest a point within max_dist (INFINITY: unbounded), e.g. to
+    // snap a click that pick() missed (rt_closest_at); returns how many of
+    // near[0 .. k) are spheres
+    uint32_t closestAt(const float point[3], float max_dist, uint32_t k, rt_near* near) {
+        uint32_t count = 0;
+        check(rt_closest_at(r_, point, max_dist, k, near, &count), r_);
+        return count;
+    }
     // first-hit G-buffer of the current camera (rt_render_gbuffer): W*H rt_hit,
     // float[4] normals and packed RGBA8 albedo in device memory, each optional
     void renderGBuffer(void* dev_hits, void* dev_normals = nullptr, void* dev_albedo = nullptr,

@@ -59,6 +59,8 @@ RT_MULTIHIT_MAX = 16      # rt_trace_rays_multi / rt_pick_multi: the largest k
 RT_OVERLAP_MAX = 16       # rt_query_overlaps / rt_overlaps_at: the largest k
 RT_OVERLAP_MORE = 0x80000000  # in a count word: the accepted set is larger than k
 RT_OVERLAP_SKIP_SELF = 1  # rt_query_overlaps flag: probe i does not report sphere index i
+RT_CLOSEST_MAX = 16       # rt_query_closest / rt_closest_at: the largest k
+RT_CLOSEST_SKIP_SELF = 1  # rt_query_closest flag: probe i leaves sphere index i out
 
 _f3 = ctypes.c_float * 3
 
@@ -208,6 +210,10 @@ class RtProbe(ctypes.Structure):
     _fields_ = [("center", _f3), ("radius", ctypes.c_float)]
 
 
+class RtNear(ctypes.Structure):
+    _fields_ = [("dist", ctypes.c_float), ("sphere", ctypes.c_uint32)]
+
+
 class RtGBuffer(ctypes.Structure):
     _fields_ = [("dev_hits", ctypes.c_void_p), ("dev_normals", ctypes.c_void_p),
                 ("dev_albedo", ctypes.c_void_p)]
@@ -258,6 +264,8 @@ SIGNATURES = {
                              ctypes.POINTER(_u32)]),
     "rt_query_overlaps": (_int, [_P, _P, _u32, _u32, _u32, _P, _P, _P, ctypes.POINTER(RtStats)]),
     "rt_overlaps_at": (_int, [_P, _fp, ctypes.c_float, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "rt_query_closest": (_int, [_P, _P, _u32, _u32, _u32, _P, _P, _P, ctypes.POINTER(RtStats)]),
+    "rt_closest_at": (_int, [_P, _fp, ctypes.c_float, _u32, ctypes.POINTER(RtNear), ctypes.POINTER(_u32)]),
     "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),

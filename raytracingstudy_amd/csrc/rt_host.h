@@ -6,7 +6,7 @@
 //   rt_frame.cpp  per-frame preparation and launch (do_render's steps: it plans a
 //                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
-//   rt_queries.cpp    ray, multi-hit and overlap queries, picking, the G-buffer
+//   rt_queries.cpp    ray, multi-hit, overlap and closest-sphere queries, picking, the G-buffer
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@
 #include "../../include/rt.h"
 #include "octree_gpu.h"
 #include "rt_bins_math.h"
+#include "rt_closest_math.h"
 #include "rt_overlap_math.h"
 #include "rt_params.h"
 #include "scene_build.h"
@@ -61,6 +62,13 @@ hipError_t launch_multihit(const FrameArgs& a, const void* rays, void* hits, voi
 hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices, void* counts,
                           uint32_t n, uint32_t k, bool skip_self, float slack_m,
                           unsigned long long* counters, hipStream_t st);
+// rt_closest.hip: n probes (rt_probe: a point and its search radius) -> n x k rt_near (probe-major,
+// the k nearest of each probe's accepted set by (key, sphere index)) and n counts (may be null)
+// against a.sc; 1 <= k <= RT_CLOSEST_MAX; slack_m: closest_slack_m of the root box; counters !=
+// null: a stats launch
+hipError_t launch_closest(const FrameArgs& a, const void* probes, void* near, void* counts, uint32_t n,
+                          uint32_t k, bool skip_self, float slack_m, unsigned long long* counters,
+                          hipStream_t st);
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
@@ -255,9 +263,11 @@ struct QueryScratch {
     DevBuf<uint2> hit;               // rt_pick: one hit
     DevBuf<uint2> multi_hits;        // rt_pick_multi: up to RT_MULTIHIT_MAX hits
     DevBuf<uint32_t> multi_count;    // ... and the count
-    DevBuf<float4> probe;            // rt_overlaps_at: the probe,
+    DevBuf<float4> probe;            // rt_overlaps_at, rt_closest_at: the probe,
     DevBuf<uint32_t> overlap_idx;    // up to RT_OVERLAP_MAX indices
     DevBuf<uint32_t> overlap_count;  // and the count word
+    DevBuf<uint2> near;              // rt_closest_at: up to RT_CLOSEST_MAX rt_near
+    DevBuf<uint32_t> near_count;     // and the count
     void release() {
         counters.release();
         ray.release();
@@ -267,6 +277,8 @@ struct QueryScratch {
         probe.release();
         overlap_idx.release();
         overlap_count.release();
+        near.release();
+        near_count.release();
     }
 };
 

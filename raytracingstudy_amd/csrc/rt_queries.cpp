@@ -1,6 +1,6 @@
 // rt_queries.cpp — the calls that read a scene without rendering a frame
-// (DESIGN.md 5.7): ray, multi-hit and sphere-overlap queries, their
-// single-item wrappers, the first-hit G-buffer.  The reference has none
+// (DESIGN.md 5.7): ray, multi-hit, sphere-overlap and closest-sphere queries,
+// their single-item wrappers, the first-hit G-buffer.  The reference has none
 // (Octree::traverse is a stub, include/octree.h:19-21; its render kernel
 // writes one colour per pixel, src/renderer.cu:57-82).  A query reads scene
 // (the G-buffer: and camera) state only: it takes no frame id, leaves the
@@ -96,10 +96,10 @@ void pick_ray(const rt_renderer* r, float u, float v, float4 ray[2]) {
 
 }  // namespace
 
-// The three single-item wrappers below (rt_pick, rt_pick_multi, rt_overlaps_at)
-// stay plain functions: their scratch buffers and copies back differ in
-// number and type, so a shared helper could hold only "order, upload one
-// record" (three lines of each), would need the rest passed in as two
+// The four single-item wrappers below (rt_pick, rt_pick_multi, rt_overlaps_at,
+// rt_closest_at) stay plain functions: their scratch buffers and copies back
+// differ in number and type, so a shared helper could hold only "order, upload
+// one record" (three lines of each), would need the rest passed in as two
 // callbacks, and would be no shorter than what it replaces.
 extern "C" {
 
@@ -245,6 +245,59 @@ int rt_overlaps_at(rt_renderer* r, const float center[3], float radius, uint32_t
     RT_HIP(r, hipMemcpyAsync(&count, r->q.overlap_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
     RT_HIP(r, hipStreamSynchronize(hs));
     memcpy(indices_out, idx, k * sizeof(uint32_t));
+    if (count_out) *count_out = count;
+    return RT_OK;
+}
+
+// Closest-sphere queries: the k scene spheres whose surfaces
+// are nearest each probe point, within its search radius.
+int rt_query_closest(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_t k, uint32_t flags,
+                     void* dev_near, void* dev_counts, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_query_closest: null handle");
+    if (k == 0 || k > RT_CLOSEST_MAX)
+        return fail(r, RT_E_INVALID, "rt_query_closest: k must be 1 .. RT_CLOSEST_MAX");
+    if (flags & ~static_cast<uint32_t>(RT_CLOSEST_SKIP_SELF))
+        return fail(r, RT_E_INVALID, "rt_query_closest: unknown flag bits");
+    if (n > 0 && (!dev_probes || !dev_near)) return fail(r, RT_E_INVALID, "rt_query_closest: null buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_query_closest: no scene (rt_set_scene first)");
+    if (n == 0) return nothing_queried(stats);
+    hipStream_t hs;
+    FrameArgs a;
+    if (const int st = query_begin(r, stream, hs, a)) return st;
+    const float slack_m = closest_slack_m(r->info.root_min, r->info.root_max);
+    // (no rays: both ray counts stay 0)
+    return query_launch(r, "rt_query_closest", hs, stats, [&](unsigned long long* ctr) {
+        return launch_closest(a, dev_probes, dev_near, dev_counts, n, k, (flags & RT_CLOSEST_SKIP_SELF) != 0,
+                              slack_m, ctr, hs);
+    });
+}
+
+int rt_closest_at(rt_renderer* r, const float point[3], float max_dist, uint32_t k, rt_near* near_out,
+                  uint32_t* count_out) {
+    if (!r || !point || !near_out) return fail(r, RT_E_INVALID, "rt_closest_at: null argument");
+    if (k == 0 || k > RT_CLOSEST_MAX)
+        return fail(r, RT_E_INVALID, "rt_closest_at: k must be 1 .. RT_CLOSEST_MAX");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_closest_at: no scene (rt_set_scene first)");
+    const float4 probe = make_float4(point[0], point[1], point[2], max_dist);
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q.probe, 1)) || (st = ensure(r, r->q.near, RT_CLOSEST_MAX)) ||
+        (st = ensure(r, r->q.near_count, 1)))
+        return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q.probe.p, &probe, sizeof(probe), hipMemcpyHostToDevice, hs));
+    if ((st = rt_query_closest(r, r->q.probe.p, 1, k, 0, r->q.near.p, r->q.near_count.p, hs, nullptr)))
+        return st;
+    uint2 h[RT_CLOSEST_MAX];
+    uint32_t count = 0;
+    RT_HIP(r, hipMemcpyAsync(h, r->q.near.p, k * sizeof(uint2), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipMemcpyAsync(&count, r->q.near_count.p, sizeof(count), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    for (uint32_t s = 0; s < k; ++s) {
+        memcpy(&near_out[s].dist, &h[s].x, sizeof(float));
+        near_out[s].sphere = h[s].y;
+    }
     if (count_out) *count_out = count;
     return RT_OK;
 }

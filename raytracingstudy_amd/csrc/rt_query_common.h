@@ -1,5 +1,5 @@
-// rt_query_common.h — what the four query units (rt_query.hip, rt_multihit.hip,
-// rt_overlap.hip, rt_gbuffer.hip) share: the stats launches' wave sum on the
+// rt_query_common.h — what the query units (rt_query.hip, rt_multihit.hip,
+// rt_overlap.hip, rt_closest.hip, rt_gbuffer.hip) share: the stats launches' wave sum on the
 // device, and the launchers' grid, stack size and k dispatch on the host.
 //
 // Two more things look shared and stay written out in each kernel: the

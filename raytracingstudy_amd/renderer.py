@@ -529,6 +529,69 @@ class KernelRenderer:
         return (word & ~_lib.RT_OVERLAP_MORE, np.array([idx[i] for i in range(k)], np.uint32),
                 bool(word & _lib.RT_OVERLAP_MORE))
 
+    # -- closest-sphere queries (rt_query_closest / rt_closest_at) ------------------
+    def query_closest_device(self, probes_ptr: int, n: int, k: int, near_ptr: int,
+                             counts_ptr: Optional[int] = None, skip_self: bool = False,
+                             stream: Optional[int] = None, stats: bool = False) -> Optional[RtStats]:
+        """rt_query_closest on buffers already on the GPU: n rt_probe (16 bytes each:
+        a point and its search radius; a scene sphere's layout) at probes_ptr ->
+        n*k rt_near at near_ptr (probe-major, each probe's k nearest spheres by
+        (signed surface distance, sphere index), then {the probe's radius,
+        RT_NO_HIT} fillers) and n uint32 counts at counts_ptr (optional).
+        Asynchronous on `stream` (None: the renderer's own) unless stats."""
+        st = RtStats() if stats else None
+        check(self._lib.rt_query_closest(self._h, ctypes.c_void_p(probes_ptr) if probes_ptr else None,
+                                         int(n), int(k),
+                                         _lib.RT_CLOSEST_SKIP_SELF if skip_self else 0,
+                                         ctypes.c_void_p(near_ptr) if near_ptr else None,
+                                         ctypes.c_void_p(counts_ptr) if counts_ptr else None,
+                                         ctypes.c_void_p(stream) if stream else None,
+                                         ctypes.byref(st) if st is not None else None), self._h)
+        return st
+
+    def query_closest(self, probes, k: int, skip_self: bool = False, stats: bool = False):
+        """The k scene spheres nearest each probe of a host (n, 4) float32 array
+        (point xyz, search radius; +inf: unbounded): uploads, runs
+        rt_query_closest, and returns (dist (n, k) float32, sphere (n, k) uint32,
+        count (n,) uint32[, RtStats]).  dist is the signed distance to the
+        sphere's surface; slots past a probe's count hold its radius and RT_NO_HIT."""
+        import torch
+        pa = np.ascontiguousarray(probes, np.float32)
+        if pa.ndim != 2 or pa.shape[1] != 4:
+            raise ValueError("probes must be an (n, 4) float32 array in rt_probe layout")
+        if not pa.flags.writeable:  # torch.from_numpy wants a writable array
+            pa = pa.copy()
+        n, k = pa.shape[0], int(k)
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_probes = torch.from_numpy(pa).to(dev)
+        d_near = torch.empty((max(n, 1), max(k, 1), 2), dtype=torch.int32, device=dev)
+        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
+        st = self.query_closest_device(d_probes.data_ptr() if n else 0, n, k,
+                                       d_near.data_ptr() if n else 0,
+                                       d_counts.data_ptr() if n else 0, skip_self, None, stats)
+        self.synchronize()
+        near = d_near[:n].cpu().numpy()
+        dist = np.ascontiguousarray(near[:, :, 0]).view(np.float32)
+        sphere = np.ascontiguousarray(near[:, :, 1]).view(np.uint32)
+        count = d_counts[:n].cpu().numpy().view(np.uint32)
+        return (dist, sphere, count, st) if stats else (dist, sphere, count)
+
+    def closest_at(self, point, max_dist: float, k: int):
+        """rt_closest_at: the k spheres nearest a point within max_dist (a missed
+        click snapping to the nearest sphere; math.inf: unbounded) ->
+        (count, dist (k,) float32, sphere (k,) uint32); slots past count hold
+        max_dist and RT_NO_HIT."""
+        k = int(k)
+        c = np.ascontiguousarray(np.asarray(point, np.float32).reshape(3))
+        near = (_lib.RtNear * max(k, 1))()
+        cnt = ctypes.c_uint32(0)
+        check(self._lib.rt_closest_at(self._h, _fptr(c), float(max_dist), k, near, ctypes.byref(cnt)),
+              self._h)
+        dist = np.array([near[i].dist for i in range(k)], np.float32)
+        sphere = np.array([near[i].sphere for i in range(k)], np.uint32)
+        return int(cnt.value), dist, sphere
+
     # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
     def render_gbuffer_device(self, hits_ptr: Optional[int] = None, normals_ptr: Optional[int] = None,
                               albedo_ptr: Optional[int] = None, stream: Optional[int] = None,
