@@ -48,6 +48,38 @@ def _vptr(a: Optional[np.ndarray]):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+def _ptr(x: Optional[int]):
+    """A device address or a stream as a pointer argument (None or 0: NULL)."""
+    return ctypes.c_void_p(x) if x else None
+
+
+def _stats_arg(stats: bool):
+    """(the RtStats a call fills or None, what to pass for it)."""
+    st = RtStats() if stats else None
+    return st, (ctypes.byref(st) if stats else None)
+
+
+def _records(a, cols: int, what: str, layout: str) -> np.ndarray:
+    """`a` as the contiguous, writable (n, cols) float32 array a batch query uploads."""
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != cols:
+        raise ValueError(f"{what} must be an (n, {cols}) float32 array in {layout} layout")
+    return a if a.flags.writeable else a.copy()  # torch.from_numpy wants a writable array
+
+
+def _split_pairs(words: np.ndarray):
+    """(..., 2) int32 records {float bits, index} (rt_hit, rt_near) ->
+    (float32 (...), uint32 (...)): two arrays of their own, bit for bit."""
+    return words[..., 0].copy().view(np.float32), words[..., 1].copy().view(np.uint32)
+
+
+def _overlap_words(words):
+    """rt_query_overlaps' count words -> (count uint32, more bool)."""
+    words = np.asarray(words, np.uint32)
+    more = np.uint32(_lib.RT_OVERLAP_MORE)
+    return words & ~more, (words & more) != 0
+
+
 def device_count() -> int:
     return int(_lib.load().rt_device_count())
 
@@ -178,10 +210,8 @@ class KernelRenderer:
                stats: bool = False) -> Optional[RtStats]:
         """render() (src/renderer.cu:143-153).  dev_ptr: a device RGBA8 buffer
         (e.g. the mapped GL PBO pointer) or None for the internal framebuffer."""
-        st = RtStats() if stats else None
-        check(self._lib.rt_render(self._h, ctypes.c_void_p(dev_ptr) if dev_ptr else None,
-                                  ctypes.c_void_p(stream) if stream else None,
-                                  ctypes.byref(st) if st is not None else None), self._h)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_render(self._h, _ptr(dev_ptr), _ptr(stream), st_arg), self._h)
         return st
 
     def resize(self, width: int, height: int) -> None:
@@ -257,10 +287,8 @@ class KernelRenderer:
         """Scene from a sphere list already in device memory (4*n float32 at
         spheres_ptr, n RGBA8 words at albedo_ptr); the octree is built on the GPU."""
         p = _octree_params(root_min, root_max, resolution, max_depth, leaf_capacity)
-        check(self._lib.rt_set_scene_device(
-            self._h, ctypes.c_void_p(spheres_ptr) if spheres_ptr else None,
-            ctypes.c_void_p(albedo_ptr) if albedo_ptr else None, int(n), ctypes.byref(p),
-            ctypes.c_void_p(stream) if stream else None), self._h)
+        check(self._lib.rt_set_scene_device(self._h, _ptr(spheres_ptr), _ptr(albedo_ptr), int(n),
+                                            ctypes.byref(p), _ptr(stream)), self._h)
         return self.scene_info()
 
     def set_scene_file(self, path: str, **octree) -> dict:
@@ -351,20 +379,35 @@ class KernelRenderer:
     def render_tiles(self, tile_ids, tile_size: int, dev_ptr: int, stream: Optional[int] = None,
                      stats: bool = False) -> Optional[RtStats]:
         ids = np.ascontiguousarray(tile_ids, np.uint32)
-        st = RtStats() if stats else None
+        st, st_arg = _stats_arg(stats)
         check(self._lib.rt_render_tiles(self._h, _vptr(ids), ids.shape[0], int(tile_size),
-                                        ctypes.c_void_p(dev_ptr),
-                                        ctypes.c_void_p(stream) if stream else None,
-                                        ctypes.byref(st) if st is not None else None), self._h)
+                                        _ptr(dev_ptr), _ptr(stream), st_arg), self._h)
         return st
 
     def unpack_tiles(self, dev_packed: int, tile_ids, tile_size: int,
                      dev_rgba8: Optional[int] = None, stream: Optional[int] = None) -> None:
         ids = np.ascontiguousarray(tile_ids, np.uint32)
-        check(self._lib.rt_unpack_tiles(self._h, ctypes.c_void_p(dev_packed), _vptr(ids),
-                                        ids.shape[0], int(tile_size),
-                                        ctypes.c_void_p(dev_rgba8) if dev_rgba8 else None,
-                                        ctypes.c_void_p(stream) if stream else None), self._h)
+        check(self._lib.rt_unpack_tiles(self._h, _ptr(dev_packed), _vptr(ids), ids.shape[0],
+                                        int(tile_size), _ptr(dev_rgba8), _ptr(stream)), self._h)
+
+    # -- batch queries on host arrays: what the four wrappers below share ----------
+    def _batch(self, records: np.ndarray, out_shapes, call):
+        """The host side of a batch query.  Uploads `records` ((n, cols) float32
+        from _records) to the handle's first device, allocates one int32 output
+        per entry of out_shapes (a record's shape; max(n, 1) records, so that a
+        bad k still reaches the library), and runs call(d_records, *d_outputs)
+        on device addresses (0 for every one when n == 0) between a torch
+        synchronize and self.synchronize().  Returns (call's result, the host
+        arrays of the outputs' first n records)."""
+        import torch
+        n = records.shape[0]
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_in = torch.from_numpy(records).to(dev)
+        d_out = [torch.empty((max(n, 1), *shape), dtype=torch.int32, device=dev) for shape in out_shapes]
+        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
+        st = call(*[d.data_ptr() if n else 0 for d in (d_in, *d_out)])
+        self.synchronize()
+        return st, [d[:n].cpu().numpy() for d in d_out]
 
     # -- ray queries (rt_trace_rays / rt_pick) -----------------------------------
     def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, kind: str = "nearest",
@@ -372,12 +415,9 @@ class KernelRenderer:
         """rt_trace_rays on buffers already on the GPU: n rt_ray (32 bytes each:
         origin, tmin, dir, tmax) at rays_ptr -> n rt_hit (t, sphere) at hits_ptr.
         Asynchronous on `stream` (None: the renderer's own) unless stats."""
-        st = RtStats() if stats else None
-        check(self._lib.rt_trace_rays(self._h, ctypes.c_void_p(rays_ptr) if rays_ptr else None,
-                                      int(n), _QUERY_KINDS[kind],
-                                      ctypes.c_void_p(hits_ptr) if hits_ptr else None,
-                                      ctypes.c_void_p(stream) if stream else None,
-                                      ctypes.byref(st) if st is not None else None), self._h)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_trace_rays(self._h, _ptr(rays_ptr), int(n), _QUERY_KINDS[kind],
+                                      _ptr(hits_ptr), _ptr(stream), st_arg), self._h)
         return st
 
     def trace_rays(self, rays, kind: str = "nearest", stats: bool = False):
@@ -385,23 +425,10 @@ class KernelRenderer:
         tmin, dir xyz, tmax): uploads, runs rt_trace_rays, and returns
         (t (n,) float32, sphere (n,) uint32[, RtStats]).  A miss has t = the
         ray's tmax and sphere = RT_NO_HIT."""
-        import torch
-        ra = np.ascontiguousarray(rays, np.float32)
-        if ra.ndim != 2 or ra.shape[1] != 8:
-            raise ValueError("rays must be an (n, 8) float32 array in rt_ray layout")
-        if not ra.flags.writeable:  # torch.from_numpy wants a writable array
-            ra = ra.copy()
-        n = ra.shape[0]
-        dev = torch.device("cuda", self.multi_info()["devices"][0])
-        d_rays = torch.from_numpy(ra).to(dev)
-        d_hits = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
-        st = self.trace_rays_device(d_rays.data_ptr() if n else 0, n, d_hits.data_ptr() if n else 0,
-                                    kind, None, stats)
-        self.synchronize()
-        hits = d_hits[:n].cpu().numpy()
-        t = np.ascontiguousarray(hits[:, 0]).view(np.float32)
-        sphere = np.ascontiguousarray(hits[:, 1]).view(np.uint32)
+        ra = _records(rays, 8, "rays", "rt_ray")
+        st, (hits,) = self._batch(ra, [(2,)], lambda d_rays, d_hits: self.trace_rays_device(
+            d_rays, len(ra), d_hits, kind, None, stats))
+        t, sphere = _split_pairs(hits)
         return (t, sphere, st) if stats else (t, sphere)
 
     def pick(self, u: float, v: float):
@@ -420,13 +447,9 @@ class KernelRenderer:
         n*k rt_hit at hits_ptr (ray-major, each ray's k nearest by (t, sphere
         index), then {tmax, RT_NO_HIT} fillers) and n uint32 counts at counts_ptr
         (optional).  Asynchronous on `stream` (None: the renderer's own) unless stats."""
-        st = RtStats() if stats else None
-        check(self._lib.rt_trace_rays_multi(self._h, ctypes.c_void_p(rays_ptr) if rays_ptr else None,
-                                            int(n), int(k),
-                                            ctypes.c_void_p(hits_ptr) if hits_ptr else None,
-                                            ctypes.c_void_p(counts_ptr) if counts_ptr else None,
-                                            ctypes.c_void_p(stream) if stream else None,
-                                            ctypes.byref(st) if st is not None else None), self._h)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_trace_rays_multi(self._h, _ptr(rays_ptr), int(n), int(k), _ptr(hits_ptr),
+                                            _ptr(counts_ptr), _ptr(stream), st_arg), self._h)
         return st
 
     def trace_rays_multi(self, rays, k: int, stats: bool = False):
@@ -434,26 +457,12 @@ class KernelRenderer:
         rt_ray layout: uploads, runs rt_trace_rays_multi, and returns
         (t (n, k) float32, sphere (n, k) uint32, count (n,) uint32[, RtStats]).
         Slots past a ray's count hold t = the ray's tmax and sphere = RT_NO_HIT."""
-        import torch
-        ra = np.ascontiguousarray(rays, np.float32)
-        if ra.ndim != 2 or ra.shape[1] != 8:
-            raise ValueError("rays must be an (n, 8) float32 array in rt_ray layout")
-        if not ra.flags.writeable:  # torch.from_numpy wants a writable array
-            ra = ra.copy()
-        n, k = ra.shape[0], int(k)
-        dev = torch.device("cuda", self.multi_info()["devices"][0])
-        d_rays = torch.from_numpy(ra).to(dev)
-        d_hits = torch.empty((max(n, 1), max(k, 1), 2), dtype=torch.int32, device=dev)
-        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
-        st = self.trace_rays_multi_device(d_rays.data_ptr() if n else 0, n, k,
-                                          d_hits.data_ptr() if n else 0,
-                                          d_counts.data_ptr() if n else 0, None, stats)
-        self.synchronize()
-        hits = d_hits[:n].cpu().numpy()
-        t = np.ascontiguousarray(hits[:, :, 0]).view(np.float32)
-        sphere = np.ascontiguousarray(hits[:, :, 1]).view(np.uint32)
-        count = d_counts[:n].cpu().numpy().view(np.uint32)
+        ra, k = _records(rays, 8, "rays", "rt_ray"), int(k)
+        st, (hits, counts) = self._batch(
+            ra, [(max(k, 1), 2), ()], lambda d_rays, d_hits, d_counts: self.trace_rays_multi_device(
+                d_rays, len(ra), k, d_hits, d_counts, None, stats))
+        t, sphere = _split_pairs(hits)
+        count = counts.view(np.uint32)
         return (t, sphere, count, st) if stats else (t, sphere, count)
 
     def pick_multi(self, u: float, v: float, k: int):
@@ -464,8 +473,7 @@ class KernelRenderer:
         hits = (_lib.RtHit * max(k, 1))()
         cnt = ctypes.c_uint32(0)
         check(self._lib.rt_pick_multi(self._h, float(u), float(v), k, hits, ctypes.byref(cnt)), self._h)
-        t = np.array([hits[i].t for i in range(k)], np.float32)
-        sphere = np.array([hits[i].sphere for i in range(k)], np.uint32)
+        t, sphere = _split_pairs(np.frombuffer(hits, np.int32).reshape(-1, 2)[:k])
         return int(cnt.value), t, sphere
 
     # -- sphere-overlap queries (rt_query_overlaps / rt_overlaps_at) ----------------
@@ -478,14 +486,11 @@ class KernelRenderer:
         ascending, then RT_NO_HIT fillers) and n count words at counts_ptr
         (optional; RT_OVERLAP_MORE set: the probe touches more than k).
         Asynchronous on `stream` (None: the renderer's own) unless stats."""
-        st = RtStats() if stats else None
-        check(self._lib.rt_query_overlaps(self._h, ctypes.c_void_p(probes_ptr) if probes_ptr else None,
-                                          int(n), int(k),
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_query_overlaps(self._h, _ptr(probes_ptr), int(n), int(k),
                                           _lib.RT_OVERLAP_SKIP_SELF if skip_self else 0,
-                                          ctypes.c_void_p(indices_ptr) if indices_ptr else None,
-                                          ctypes.c_void_p(counts_ptr) if counts_ptr else None,
-                                          ctypes.c_void_p(stream) if stream else None,
-                                          ctypes.byref(st) if st is not None else None), self._h)
+                                          _ptr(indices_ptr), _ptr(counts_ptr), _ptr(stream), st_arg),
+              self._h)
         return st
 
     def query_overlaps(self, probes, k: int, skip_self: bool = False, stats: bool = False):
@@ -493,26 +498,12 @@ class KernelRenderer:
         radius) touches: uploads, runs rt_query_overlaps, and returns
         (indices (n, k) uint32, count (n,) uint32, more (n,) bool[, RtStats]).
         Slots past a probe's count hold RT_NO_HIT; more: it touches more than k."""
-        import torch
-        pa = np.ascontiguousarray(probes, np.float32)
-        if pa.ndim != 2 or pa.shape[1] != 4:
-            raise ValueError("probes must be an (n, 4) float32 array in rt_probe layout")
-        if not pa.flags.writeable:  # torch.from_numpy wants a writable array
-            pa = pa.copy()
-        n, k = pa.shape[0], int(k)
-        dev = torch.device("cuda", self.multi_info()["devices"][0])
-        d_probes = torch.from_numpy(pa).to(dev)
-        d_idx = torch.empty((max(n, 1), max(k, 1)), dtype=torch.int32, device=dev)
-        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
-        st = self.query_overlaps_device(d_probes.data_ptr() if n else 0, n, k,
-                                        d_idx.data_ptr() if n else 0,
-                                        d_counts.data_ptr() if n else 0, skip_self, None, stats)
-        self.synchronize()
-        indices = d_idx[:n].cpu().numpy().view(np.uint32)
-        words = d_counts[:n].cpu().numpy().view(np.uint32)
-        count = words & np.uint32(~_lib.RT_OVERLAP_MORE & 0xFFFFFFFF)
-        more = (words & np.uint32(_lib.RT_OVERLAP_MORE)) != 0
+        pa, k = _records(probes, 4, "probes", "rt_probe"), int(k)
+        st, (indices, words) = self._batch(
+            pa, [(max(k, 1),), ()], lambda d_probes, d_idx, d_counts: self.query_overlaps_device(
+                d_probes, len(pa), k, d_idx, d_counts, skip_self, None, stats))
+        indices = indices.view(np.uint32)
+        count, more = _overlap_words(words.view(np.uint32))
         return (indices, count, more, st) if stats else (indices, count, more)
 
     def overlaps_at(self, center, radius: float, k: int):
@@ -525,9 +516,8 @@ class KernelRenderer:
         cnt = ctypes.c_uint32(0)
         check(self._lib.rt_overlaps_at(self._h, _fptr(c), float(radius), k, idx, ctypes.byref(cnt)),
               self._h)
-        word = int(cnt.value)
-        return (word & ~_lib.RT_OVERLAP_MORE, np.array([idx[i] for i in range(k)], np.uint32),
-                bool(word & _lib.RT_OVERLAP_MORE))
+        count, more = _overlap_words(cnt.value)
+        return int(count), np.frombuffer(idx, np.uint32)[:k].copy(), bool(more)
 
     # -- closest-sphere queries (rt_query_closest / rt_closest_at) ------------------
     def query_closest_device(self, probes_ptr: int, n: int, k: int, near_ptr: int,
@@ -539,14 +529,11 @@ class KernelRenderer:
         (signed surface distance, sphere index), then {the probe's radius,
         RT_NO_HIT} fillers) and n uint32 counts at counts_ptr (optional).
         Asynchronous on `stream` (None: the renderer's own) unless stats."""
-        st = RtStats() if stats else None
-        check(self._lib.rt_query_closest(self._h, ctypes.c_void_p(probes_ptr) if probes_ptr else None,
-                                         int(n), int(k),
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_query_closest(self._h, _ptr(probes_ptr), int(n), int(k),
                                          _lib.RT_CLOSEST_SKIP_SELF if skip_self else 0,
-                                         ctypes.c_void_p(near_ptr) if near_ptr else None,
-                                         ctypes.c_void_p(counts_ptr) if counts_ptr else None,
-                                         ctypes.c_void_p(stream) if stream else None,
-                                         ctypes.byref(st) if st is not None else None), self._h)
+                                         _ptr(near_ptr), _ptr(counts_ptr), _ptr(stream), st_arg),
+              self._h)
         return st
 
     def query_closest(self, probes, k: int, skip_self: bool = False, stats: bool = False):
@@ -555,26 +542,12 @@ class KernelRenderer:
         rt_query_closest, and returns (dist (n, k) float32, sphere (n, k) uint32,
         count (n,) uint32[, RtStats]).  dist is the signed distance to the
         sphere's surface; slots past a probe's count hold its radius and RT_NO_HIT."""
-        import torch
-        pa = np.ascontiguousarray(probes, np.float32)
-        if pa.ndim != 2 or pa.shape[1] != 4:
-            raise ValueError("probes must be an (n, 4) float32 array in rt_probe layout")
-        if not pa.flags.writeable:  # torch.from_numpy wants a writable array
-            pa = pa.copy()
-        n, k = pa.shape[0], int(k)
-        dev = torch.device("cuda", self.multi_info()["devices"][0])
-        d_probes = torch.from_numpy(pa).to(dev)
-        d_near = torch.empty((max(n, 1), max(k, 1), 2), dtype=torch.int32, device=dev)
-        d_counts = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)  # the upload ran on torch's stream
-        st = self.query_closest_device(d_probes.data_ptr() if n else 0, n, k,
-                                       d_near.data_ptr() if n else 0,
-                                       d_counts.data_ptr() if n else 0, skip_self, None, stats)
-        self.synchronize()
-        near = d_near[:n].cpu().numpy()
-        dist = np.ascontiguousarray(near[:, :, 0]).view(np.float32)
-        sphere = np.ascontiguousarray(near[:, :, 1]).view(np.uint32)
-        count = d_counts[:n].cpu().numpy().view(np.uint32)
+        pa, k = _records(probes, 4, "probes", "rt_probe"), int(k)
+        st, (near, counts) = self._batch(
+            pa, [(max(k, 1), 2), ()], lambda d_probes, d_near, d_counts: self.query_closest_device(
+                d_probes, len(pa), k, d_near, d_counts, skip_self, None, stats))
+        dist, sphere = _split_pairs(near)
+        count = counts.view(np.uint32)
         return (dist, sphere, count, st) if stats else (dist, sphere, count)
 
     def closest_at(self, point, max_dist: float, k: int):
@@ -588,8 +561,7 @@ class KernelRenderer:
         cnt = ctypes.c_uint32(0)
         check(self._lib.rt_closest_at(self._h, _fptr(c), float(max_dist), k, near, ctypes.byref(cnt)),
               self._h)
-        dist = np.array([near[i].dist for i in range(k)], np.float32)
-        sphere = np.array([near[i].sphere for i in range(k)], np.uint32)
+        dist, sphere = _split_pairs(np.frombuffer(near, np.int32).reshape(-1, 2)[:k])
         return int(cnt.value), dist, sphere
 
     # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
@@ -601,10 +573,8 @@ class KernelRenderer:
         normals at normals_ptr, W*H packed RGBA8 at albedo_ptr.  Asynchronous on
         `stream` (None: the renderer's own) unless stats."""
         g = _lib.RtGBuffer(hits_ptr or None, normals_ptr or None, albedo_ptr or None)
-        st = RtStats() if stats else None
-        check(self._lib.rt_render_gbuffer(self._h, ctypes.byref(g),
-                                          ctypes.c_void_p(stream) if stream else None,
-                                          ctypes.byref(st) if st is not None else None), self._h)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_render_gbuffer(self._h, ctypes.byref(g), _ptr(stream), st_arg), self._h)
         return st
 
     def render_gbuffer(self, normals: bool = True, albedo: bool = True, stats: bool = False) -> dict:
@@ -622,9 +592,8 @@ class KernelRenderer:
         st = self.render_gbuffer_device(d_hits.data_ptr(), d_nrm.data_ptr() if normals else None,
                                         d_alb.data_ptr() if albedo else None, None, stats)
         self.synchronize()
-        hits = d_hits.cpu().numpy()
-        out = {"t": np.ascontiguousarray(hits[..., 0]).view(np.float32),
-               "sphere": np.ascontiguousarray(hits[..., 1]).view(np.uint32)}
+        t, sphere = _split_pairs(d_hits.cpu().numpy())
+        out = {"t": t, "sphere": sphere}
         if normals:
             out["normal"] = d_nrm.cpu().numpy()
         if albedo:

@@ -5,35 +5,25 @@ reference runs once per scene at k = 16; a smaller k's answer is its first k
 columns.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import raytracingstudy_amd as rt
 from raytracingstudy_amd import _lib
-from raytracingstudy_amd.camera import scene_pose
 
 import closest_ref as cr
 import overlap_ref as ov
+from query_scaffold import CAM_H, CAM_W, assert_frames_undisturbed
+from query_scaffold import bits as _bits
+from query_scaffold import scene_renderer as _renderer
 
 pytestmark = pytest.mark.gpu
 
 NO_HIT = cr.NO_HIT
 INF = cr.INF
 KS = (1, 2, 3, 4, 8, 16)
-CAM_W, CAM_H = 96, 64
-
-
-def _renderer(name, w=CAM_W, h=CAM_H, **kw):
-    r = rt.KernelRenderer(w, h, mode="scene", **kw)
-    r.resize(w, h)
-    r.setPosition(scene_pose())
-    r.set_scene(ov.spheres(name), None, **ov.TREES[name])
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_answer(got, exp, pr, k, what=""):
@@ -264,27 +254,12 @@ def test_closest_queries_do_not_disturb_frames(gpu):
     counts what it counts without them (accumulated samples included)."""
     pr = cr.probes("A")[:300]
 
-    def frames(query):
-        out = []
-        with _renderer("A", spp=2, progressive=True) as r:
-            for _ in range(3):
-                r.render()
-                out.append(r.readback())
-                if query:
-                    r.query_closest(pr, 4, stats=True)
-                    r.query_closest(pr, 16, skip_self=True)
-                    r.closest_at((0.6, 0.6, 0.6), float("inf"), 3)
-            st = r.render(stats=True)
-            out.append(r.readback())
-        return out, (st.primary_rays, st.shadow_rays, st.nodes_visited, st.prims_tested,
-                     st.samples_per_pixel)
+    def queries(r):
+        r.query_closest(pr, 4, stats=True)
+        r.query_closest(pr, 16, skip_self=True)
+        r.closest_at((0.6, 0.6, 0.6), float("inf"), 3)
 
-    plain, st_plain = frames(False)
-    mixed, st_mixed = frames(True)
-    for a, b in zip(plain, mixed):
-        assert np.array_equal(a, b)
-    assert st_plain == st_mixed and st_plain[4] == 8
-    assert not np.array_equal(plain[0], plain[2])  # the sums did accumulate
+    assert_frames_undisturbed(functools.partial(_renderer, "A"), queries)
 
 
 def test_zero_probes_and_argument_errors(gpu):

@@ -16,21 +16,14 @@ from raytracingstudy_amd.camera import scene_pose
 
 import multihit_ref as mr
 import tie_scenes as ts
+from query_scaffold import CAM_H, CAM_W, assert_frames_undisturbed
+from query_scaffold import scene_renderer as _renderer  # overlap_ref's A, B and D are multihit_ref's
 
 pytestmark = pytest.mark.gpu
 
 NO_HIT = mr.NO_HIT
 INF = np.float32(np.inf)
 KS = (1, 2, 3, 4, 8, 16)
-CAM_W, CAM_H = 96, 64
-
-
-def _renderer(name, w=CAM_W, h=CAM_H, **kw):
-    r = rt.KernelRenderer(w, h, mode="scene", **kw)
-    r.resize(w, h)
-    r.setPosition(scene_pose())
-    r.set_scene(mr.spheres(name), None, **mr.tree(name))
-    return r
 
 
 def _assert_answer(got, exp, rays, k, what=""):
@@ -289,27 +282,12 @@ def test_multi_queries_do_not_disturb_frames(gpu):
     counts what it counts without them (accumulated samples included)."""
     rays = mr.rays("A")[:257]
 
-    def frames(query):
-        out = []
-        with _renderer("A", spp=2, progressive=True) as r:
-            for _ in range(3):
-                r.render()
-                out.append(r.readback())
-                if query:
-                    r.trace_rays_multi(rays, 4, stats=True)
-                    r.trace_rays_multi(rays, 16)
-                    r.pick_multi(40.0, 30.0, 3)
-            st = r.render(stats=True)
-            out.append(r.readback())
-        return out, (st.primary_rays, st.shadow_rays, st.nodes_visited, st.prims_tested,
-                     st.samples_per_pixel)
+    def queries(r):
+        r.trace_rays_multi(rays, 4, stats=True)
+        r.trace_rays_multi(rays, 16)
+        r.pick_multi(40.0, 30.0, 3)
 
-    plain, st_plain = frames(False)
-    mixed, st_mixed = frames(True)
-    for a, b in zip(plain, mixed):
-        assert np.array_equal(a, b)
-    assert st_plain == st_mixed and st_plain[4] == 8
-    assert not np.array_equal(plain[0], plain[2])  # the sums did accumulate
+    assert_frames_undisturbed(functools.partial(_renderer, "A"), queries)
 
 
 def test_multi_device_handle_answers_from_device_0(gpu):

@@ -18,6 +18,8 @@ import raytracingstudy_amd as rt
 from raytracingstudy_amd import _lib
 from raytracingstudy_amd.camera import scene_pose
 
+from query_scaffold import CAM_H, CAM_W, assert_frames_undisturbed, scene_renderer
+
 pytestmark = pytest.mark.gpu
 
 NO_HIT = 0xFFFFFFFF
@@ -27,7 +29,6 @@ INF = np.float32(np.inf)
 SCENES = {"A": dict(n=1000, max_depth=7, leaf_capacity=8),
           "B": dict(n=20000, max_depth=12, leaf_capacity=2)}
 N_SURFACE, N_CAMERA, N_OUTSIDE = 2048, 1024, 1061  # 4133 rays: the largest size tested
-CAM_W, CAM_H = 96, 64
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,14 +106,12 @@ def _expected(name, kind):
     return out
 
 
-def _renderer(name, w=CAM_W, h=CAM_H, **kw):
-    sp, al = _spheres(name)
-    r = rt.KernelRenderer(w, h, mode="scene", **kw)
-    r.resize(w, h)
-    r.setPosition(scene_pose())
-    r.set_scene(sp, al, max_depth=SCENES[name]["max_depth"],
-                leaf_capacity=SCENES[name]["leaf_capacity"])
-    return r
+def _scene(name):
+    tree = {k: SCENES[name][k] for k in ("max_depth", "leaf_capacity")}
+    return (*_spheres(name), tree)
+
+
+_renderer = functools.partial(scene_renderer, scene=_scene)
 
 
 def _assert_equal(t, sphere, exp, n=None):
@@ -290,27 +289,12 @@ def test_queries_do_not_disturb_frames(gpu):
     what it counts without one."""
     rays = _rays("A")[:257]
 
-    def frames(query):
-        out = []
-        with _renderer("A", spp=2, progressive=True) as r:
-            for _ in range(3):
-                r.render()
-                out.append(r.readback())
-                if query:
-                    r.trace_rays(rays, "nearest", stats=True)
-                    r.trace_rays(rays, "any")
-                    r.pick(40.0, 30.0)
-            st = r.render(stats=True)
-            out.append(r.readback())
-        return out, (st.primary_rays, st.shadow_rays, st.nodes_visited, st.prims_tested,
-                     st.samples_per_pixel)
+    def queries(r):
+        r.trace_rays(rays, "nearest", stats=True)
+        r.trace_rays(rays, "any")
+        r.pick(40.0, 30.0)
 
-    plain, st_plain = frames(False)
-    mixed, st_mixed = frames(True)
-    for a, b in zip(plain, mixed):
-        assert np.array_equal(a, b)
-    assert st_plain == st_mixed and st_plain[4] == 8
-    assert not np.array_equal(plain[0], plain[2])  # the sums did accumulate
+    assert_frames_undisturbed(functools.partial(_renderer, "A"), queries)
 
 
 def test_device_pointers_on_a_torch_stream(gpu, oracle):

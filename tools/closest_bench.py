@@ -35,7 +35,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import raytracingstudy_amd as rt  # noqa: E402
-from raytracingstudy_amd.camera import scene_pose  # noqa: E402
+from tools import query_bench_common as qb  # noqa: E402
 
 
 def torch_closest(torch, d_sp, d_pr, k, chunk, skip_self):
@@ -79,23 +79,14 @@ def main():
     import torch
     if rt.device_count() == 0:
         sys.exit("closest_bench: no HIP device visible (rates are measured on the GPU only)")
-    cfg = rt.CONFIGS[args.config]
     n = 1 << args.log2_probes
-    sp, al = rt.configs.scene_spheres(cfg, rt.SEED)
-    sp = np.ascontiguousarray(sp, np.float32)
-    r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=cfg.spp)
-    r.resize(cfg.width, cfg.height)
-    r.setPosition(scene_pose())
-    info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    r, sp, info, _ = qb.scene_renderer(args.config)
     g = np.random.default_rng(12345)
-    lo, hi = np.array(info["root_min"], np.float32), np.array(info["root_max"], np.float32)
     mean_r = float(sp[:, 3].mean())
     own = sp.copy()
     own[:, 3] = np.inf
-    points = np.zeros((n, 4), np.float32)
-    points[:, :3] = g.uniform(lo, hi, (n, 3))
-    points[:, 3] = np.inf
-    balls = points.copy()
+    points = qb.root_box_probes(g, info, n, np.inf)
+    balls = points.copy()  # the same centres: one draw
     balls[:, 3] = mean_r
     sets = {"neighbours": (own, True), "points": (points, False), "mean_r": (balls, False)}
     cases = [(name, k) for name in sets for k in ks]
@@ -116,15 +107,6 @@ def main():
         return r.query_overlaps_device(dev["mean_r"].data_ptr(), n, k, d_near.data_ptr(), d_cnt.data_ptr(),
                                        stream=stream.cuda_stream, stats=stats)
 
-    def timed(fn, st):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        fn()
-        e1.record(st)
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     ms = {c: [] for c in cases}
     tms = {c: [] for c in cases}
     oms = {k: [] for k in ks}
@@ -132,19 +114,18 @@ def main():
     cur = torch.cuda.current_stream()
     for rnd in range(args.warmup + args.rounds):
         for name, k in cases:
-            t = timed(lambda: launch(name, k), stream)
-            tt = timed(lambda: torch_closest(torch, d_sp, dev[name][:tn[name]], k, args.torch_chunk,
-                                             sets[name][1]), cur)
+            t = qb.event_ms(lambda: launch(name, k), stream)
+            tt = qb.event_ms(lambda: torch_closest(torch, d_sp, dev[name][:tn[name]], k, args.torch_chunk,
+                                                   sets[name][1]), cur)
             if rnd >= args.warmup:
                 ms[name, k].append(t)
                 tms[name, k].append(tt)
         for k in ks:
-            t = timed(lambda: launch_overlap(k), stream)
+            t = qb.event_ms(lambda: launch_overlap(k), stream)
             if rnd >= args.warmup:
                 oms[k].append(t)
     out = {"config": args.config, "ks": ks, "rounds": args.rounds, "warmup": args.warmup,
-           "scene": {q: info[q] for q in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
-                                          "cell_table_depth")},
+           "scene": qb.scene_summary(info),
            "mean_radius": round(mean_r, 6), "cell_table_entry": "not built"}
     for name, k in cases:
         p, skip = sets[name]
@@ -162,14 +143,13 @@ def main():
         rate, trate = m / med * 1e3, t_n / tmed * 1e3
         out[f"{name}_k{k}"] = {
             "probes": m, "k": k, "skip_self": skip, "radius": "inf" if name != "mean_r" else round(mean_r, 6),
-            "ms_median": round(med, 4), "ms_min": round(min(ms[name, k]), 4), "ms_max": round(max(ms[name, k]), 4),
+            **qb.ms_row(ms[name, k]),
             "Mprobes_s": round(rate / 1e6, 3),
             "mean_count": round(float(count.float().mean()), 4),
             "nodes_per_probe": round(st.nodes_visited / m, 3),
             "tests_per_probe": round(st.prims_tested / m, 3),
             "stats_launch_ms": round(float(st.ms), 4),
-            "torch": {"probes": t_n, "chunk": args.torch_chunk, "ms_median": round(tmed, 3),
-                      "ms_min": round(min(tms[name, k]), 3), "ms_max": round(max(tms[name, k]), 3),
+            "torch": {"probes": t_n, "chunk": args.torch_chunk, **qb.ms_row(tms[name, k], 3),
                       "Mprobes_s": round(trate / 1e6, 4), "same_answer": same,
                       "rows_without_ties": int(untied.sum())},
             "speedup_vs_torch": round(rate / trate, 1)}
@@ -178,8 +158,7 @@ def main():
         r.synchronize()
         med = float(np.median(oms[k]))
         out[f"overlaps_mean_r_k{k}"] = {
-            "probes": n, "k": k, "ms_median": round(med, 4), "ms_min": round(min(oms[k]), 4),
-            "ms_max": round(max(oms[k]), 4), "Mprobes_s": round(n / med * 1e3 / 1e6, 3),
+            "probes": n, "k": k, **qb.ms_row(oms[k]), "Mprobes_s": round(n / med * 1e3 / 1e6, 3),
             "nodes_per_probe": round(st.nodes_visited / n, 3), "tests_per_probe": round(st.prims_tested / n, 3)}
     print(json.dumps(out))
     r.close()

@@ -31,8 +31,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import raytracingstudy_amd as rt  # noqa: E402
-from raytracingstudy_amd.camera import scene_pose  # noqa: E402
-from tools.query_bench import camera_rays  # noqa: E402
+from tools import query_bench_common as qb  # noqa: E402
 
 
 def main():
@@ -45,18 +44,12 @@ def main():
     import torch
     if rt.device_count() == 0:
         sys.exit("gbuffer_bench: no HIP device visible (times are measured on the GPU only)")
-    cfg = rt.CONFIGS[args.config]
-    w, h = cfg.width, cfg.height
+    r, _, info, pose = qb.scene_renderer(args.config)
+    w, h = r.width, r.height
     n = w * h
-    sp, al = rt.configs.scene_spheres(cfg, rt.SEED)
-    r = rt.KernelRenderer(w, h, mode="scene", spp=cfg.spp)
-    r.resize(w, h)
-    pose = scene_pose()
-    r.setPosition(pose)
-    info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
     _, K = r.camera()
     stream = torch.cuda.Stream()
-    d_rays = torch.from_numpy(camera_rays(n, w, h, pose, K)).cuda()
+    d_rays = torch.from_numpy(qb.camera_rays(n, w, h, pose, K)).cuda()
     d_hits = torch.empty((n, 2), dtype=torch.int32, device="cuda")
     d_qhits = torch.empty((n, 2), dtype=torch.int32, device="cuda")
     d_nrm = torch.empty((n, 4), dtype=torch.float32, device="cuda")
@@ -72,9 +65,7 @@ def main():
     }
     out = {"config": args.config, "width": w, "height": h, "rays": n, "reps": args.reps,
            "warmup": args.warmup,
-           "scene": {k: info[k] for k in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
-                                          "cell_table_depth")},
-           "passes": []}
+           "scene": qb.scene_summary(info), "passes": []}
     for _ in range(args.passes):
         for _ in range(args.warmup):
             for launch in rows.values():
@@ -82,16 +73,8 @@ def main():
         ms = {k: [] for k in rows}
         for _ in range(args.reps):
             for k, launch in rows.items():
-                e0 = torch.cuda.Event(enable_timing=True)
-                e1 = torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                launch()
-                e1.record(stream)
-                e1.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-        out["passes"].append({k: {"ms_median": round(float(np.median(v)), 4), "ms_min": round(min(v), 4),
-                                  "ms_max": round(max(v), 4),
-                                  "Mrays_s": round(n / float(np.median(v)) / 1e3, 1)}
+                ms[k].append(qb.event_ms(launch, stream))
+        out["passes"].append({k: {**qb.ms_row(v), "Mrays_s": round(n / float(np.median(v)) / 1e3, 1)}
                               for k, v in ms.items()})
     st = r.render_gbuffer_device(d_hits.data_ptr(), stream=s, stats=True)
     sq = r.trace_rays_device(d_rays.data_ptr(), n, d_qhits.data_ptr(), "nearest", stream=s, stats=True)

@@ -32,7 +32,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import raytracingstudy_amd as rt  # noqa: E402
-from raytracingstudy_amd.camera import scene_pose  # noqa: E402
+from tools import query_bench_common as qb  # noqa: E402
 
 
 def torch_overlaps(torch, d_sp, d_pr, k, chunk, skip_self):
@@ -73,23 +73,13 @@ def main():
     import torch
     if rt.device_count() == 0:
         sys.exit("overlap_bench: no HIP device visible (rates are measured on the GPU only)")
-    cfg = rt.CONFIGS[args.config]
     k = args.k
     n = 1 << args.log2_probes
-    sp, al = rt.configs.scene_spheres(cfg, rt.SEED)
-    sp = np.ascontiguousarray(sp, np.float32)
-    r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=cfg.spp)
-    r.resize(cfg.width, cfg.height)
-    r.setPosition(scene_pose())
-    info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    r, sp, info, _ = qb.scene_renderer(args.config)
     g = np.random.default_rng(12345)
-    lo, hi = np.array(info["root_min"], np.float32), np.array(info["root_max"], np.float32)
     mean_r = float(sp[:, 3].mean())
-    points = np.zeros((n, 4), np.float32)
-    points[:, :3] = g.uniform(lo, hi, (n, 3))
-    balls = np.zeros((n, 4), np.float32)
-    balls[:, :3] = g.uniform(lo, hi, (n, 3))
-    balls[:, 3] = mean_r
+    points = qb.root_box_probes(g, info, n, 0.0)
+    balls = qb.root_box_probes(g, info, n, mean_r)  # a second draw: other centres than points'
     cases = {"contacts": (sp, True), "points": (points, False), "mean_r": (balls, False)}
     stream = torch.cuda.Stream()
     d_sp = torch.from_numpy(sp).cuda()
@@ -104,30 +94,20 @@ def main():
         return r.query_overlaps_device(dev[name].data_ptr(), len(p), k, d_idx.data_ptr(), d_cnt.data_ptr(),
                                        skip_self=skip, stream=stream.cuda_stream, stats=stats)
 
-    def timed(fn, st):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(st)
-        fn()
-        e1.record(st)
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
     ms = {name: [] for name in cases}
     tms = {name: [] for name in cases}
     tn = {name: min(args.torch_probes, len(cases[name][0])) for name in cases}
     cur = torch.cuda.current_stream()
     for rnd in range(args.warmup + args.rounds):
         for name in cases:
-            t = timed(lambda: launch(name), stream)
-            tt = timed(lambda: torch_overlaps(torch, d_sp, dev[name][:tn[name]], k, args.torch_chunk,
-                                              cases[name][1]), cur)
+            t = qb.event_ms(lambda: launch(name), stream)
+            tt = qb.event_ms(lambda: torch_overlaps(torch, d_sp, dev[name][:tn[name]], k, args.torch_chunk,
+                                                    cases[name][1]), cur)
             if rnd >= args.warmup:
                 ms[name].append(t)
                 tms[name].append(tt)
     out = {"config": args.config, "k": k, "rounds": args.rounds, "warmup": args.warmup,
-           "scene": {q: info[q] for q in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
-                                          "cell_table_depth")},
+           "scene": qb.scene_summary(info),
            "mean_radius": round(mean_r, 6), "cell_table_entry": "not built"}
     for name, (p, skip) in cases.items():
         m = len(p)
@@ -141,16 +121,14 @@ def main():
         med, tmed = float(np.median(ms[name])), float(np.median(tms[name]))
         rate, trate = m / med * 1e3, tn[name] / tmed * 1e3
         out[name] = {
-            "probes": m, "skip_self": skip,
-            "ms_median": round(med, 4), "ms_min": round(min(ms[name]), 4), "ms_max": round(max(ms[name]), 4),
+            "probes": m, "skip_self": skip, **qb.ms_row(ms[name]),
             "Mprobes_s": round(rate / 1e6, 3),
             "mean_count": round(float((words & 0x7FFFFFFF).mean()), 4),
             "more_fraction": round(float((words >> 31).mean()), 6),
             "nodes_per_probe": round(st.nodes_visited / m, 3),
             "prims_per_probe": round(st.prims_tested / m, 3),
             "stats_launch_ms": round(float(st.ms), 4),
-            "torch": {"probes": tn[name], "chunk": args.torch_chunk, "ms_median": round(tmed, 3),
-                      "ms_min": round(min(tms[name]), 3), "ms_max": round(max(tms[name]), 3),
+            "torch": {"probes": tn[name], "chunk": args.torch_chunk, **qb.ms_row(tms[name], 3),
                       "Mprobes_s": round(trate / 1e6, 4), "same_answer": same},
             "speedup_vs_torch": round(rate / trate, 1)}
     print(json.dumps(out))

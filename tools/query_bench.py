@@ -30,22 +30,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import raytracingstudy_amd as rt  # noqa: E402
-from raytracingstudy_amd.camera import scene_pose  # noqa: E402
-
-
-def camera_rays(n: int, w: int, h: int, pose: np.ndarray, K: np.ndarray) -> np.ndarray:
-    """Camera::getRay (include/camera.h:24-41) at pixel centres, row-major, f32."""
-    f = np.float32
-    i = np.arange(n, dtype=np.int64) % (w * h)
-    u, v = (i % w).astype(f), (i // w).astype(f)
-    dx, dy = (u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1]
-    d = np.stack([pose[0, c] * dx + pose[1, c] * dy + pose[2, c] for c in range(3)], 1).astype(f)
-    d /= np.sqrt((d * d).sum(1, dtype=f))[:, None]
-    rays = np.zeros((n, 8), f)
-    rays[:, :3] = pose[3, :3]
-    rays[:, 4:7] = d
-    rays[:, 7] = np.inf
-    return rays
+from tools import query_bench_common as qb  # noqa: E402
 
 
 def surface_rays(n: int, sp: np.ndarray, seed: int) -> np.ndarray:
@@ -79,36 +64,20 @@ def main():
     import torch
     if rt.device_count() == 0:
         sys.exit("query_bench: no HIP device visible (rates are measured on the GPU only)")
-    cfg = rt.CONFIGS[args.config]
     n = 1 << args.log2_rays
-    sp, al = rt.configs.scene_spheres(cfg, rt.SEED)
-    r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=cfg.spp)
-    r.resize(cfg.width, cfg.height)
-    pose = scene_pose()
-    r.setPosition(pose)
-    info = r.set_scene(sp, al, max_depth=cfg.max_depth, leaf_capacity=cfg.leaf_capacity)
+    r, sp, info, pose = qb.scene_renderer(args.config)
     _, K = r.camera()
-    sets = {"coherent": camera_rays(n, cfg.width, cfg.height, pose, K),
+    sets = {"coherent": qb.camera_rays(n, r.width, r.height, pose, K),
             "incoherent": surface_rays(n, sp, 12345)}
     stream = torch.cuda.Stream()
     d_hits = torch.empty((n, 2), dtype=torch.int32, device="cuda")
     out = {"config": args.config, "rays": n, "reps": args.reps, "warmup": args.warmup,
-           "scene": {k: info[k] for k in ("n_spheres", "n_nodes", "n_prim_refs", "depth_reached",
-                                          "cell_table_depth")}}
+           "scene": qb.scene_summary(info)}
 
     def timed(launch):
         for _ in range(args.warmup):
             launch()
-        ms = []
-        for _ in range(args.reps):
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            launch()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        return ms
+        return [qb.event_ms(launch, stream) for _ in range(args.reps)]
 
     d_mhits = d_counts = None
     if multi_ks:
@@ -127,7 +96,7 @@ def main():
             hit = float((d_hits[:, 1] != -1).float().mean().item())
             med = float(np.median(ms))
             out[f"{name}_{kind}"] = {
-                "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                **qb.ms_row(ms),
                 "Mrays_s": round(n / med / 1e3, 1), "hit_fraction": round(hit, 4),
                 "nodes_per_ray": round(st.nodes_visited / n, 3),
                 "prims_per_ray": round(st.prims_tested / n, 3),
@@ -142,7 +111,7 @@ def main():
                                            d_counts.data_ptr(), stream=stream.cuda_stream, stats=True)
             med = float(np.median(ms))
             out[f"{name}_multi{k}"] = {
-                "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                **qb.ms_row(ms),
                 "Mrays_s": round(n / med / 1e3, 1),
                 "mean_count": round(float(d_counts.float().mean().item()), 4),
                 "nodes_per_ray": round(st.nodes_visited / n, 3),
