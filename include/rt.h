@@ -44,6 +44,8 @@
  *     the octree which spheres touch a ball)
  *   (none: as above; nothing asks which spheres are       rt_query_closest / rt_closest_at
  *     nearest to a point)
+ *   (none: as above; nothing asks what a moving ball      rt_sweep_spheres / rt_sweep_at /
+ *     touches first)                                        rt_pick_thick
  *   (none: no error reporting, all void)                  rt_last_error
  *
  * Threading: one handle per host thread / stream; calls on one handle are not
@@ -563,6 +565,61 @@ int rt_query_closest(rt_renderer* r, const void* dev_probes, uint32_t n, uint32_
  * (INTEGRATION.md). */
 int rt_closest_at(rt_renderer* r, const float point[3], float max_dist, uint32_t k,
                   rt_near* near_out, uint32_t* count_out);
+
+/* ---- swept-sphere queries --------------------------------------------------- */
+/* The first scene sphere a moving ball touches: a simulation's time of impact
+ * (continuous collision detection), a character or probe of finite size moved
+ * through the scene, a lidar beam with width, a cursor of finite radius that
+ * hits the spheres rt_pick's thin ray misses.  The reference has no counterpart
+ * (Octree::traverse is a stub, include/octree.h:19-21).
+ * A cast is an rt_ray plus a radius R: a ball of radius R has its centre at
+ * origin + t * dir.  For scene sphere (c, r), s = r + R is one f32 add, and the
+ * test is rt_trace_rays' own intersection test against the sphere (c, s): the
+ * same operations in the same order, the same window tmin < t < tmax, the same
+ * fall-through to the far root when the near root is not past tmin.  The
+ * answer is the smallest t, then the smallest sphere index (RT_QUERY_NEAREST's
+ * rule), as an rt_hit; a miss is {the cast's tmax, RT_NO_HIT}.  As r + 0.0f is
+ * r, a valid cast with R = 0 answers exactly as rt_trace_rays(...,
+ * RT_QUERY_NEAREST), bit for bit.
+ * Validity: a cast with a NaN or infinite origin or direction component misses,
+ * as in rt_trace_rays; so does one whose R is not finite or is < 0 (R = -0 is
+ * 0).  Unlike rt_trace_rays, `dir` has to be of unit length, as R is in world
+ * units and t therefore has to be: a cast with
+ * |((dx*dx + dy*dy) + dz*dz) - 1| > 2^-18, computed in f32 in that order,
+ * misses too.  A direction normalised in f32 (each component divided by the
+ * f32 length) passes: it is within 2^-22 of unit length.
+ * flags:
+ *   RT_SWEEP_ENTRY_ONLY  only the near root counts: a sphere the ball already
+ *       touches at tmin (its near root is not past tmin) is not reported; those
+ *       spheres are rt_query_overlaps' answer.  Without the flag the ray rule
+ *       holds and the far root is reported, like a camera inside a sphere.
+ *   RT_SWEEP_SKIP_SELF   cast i leaves sphere index i out (a cast with i >=
+ *       n_spheres skips nothing): the scene's centres as origins, its radii as
+ *       R and a step's velocities as directions give each sphere's first impact
+ *       of that step.
+ *   dev_rays   n rt_ray in device memory.
+ *   dev_radii  n floats in device memory, cast i's R; NULL: every cast uses
+ *              `radius`.
+ *   dev_hits   n rt_hit in device memory; every one is written.
+ * stream, ordering, stats and error codes as rt_query_closest: asynchronous
+ * unless stats != NULL, ordered after the handle's earlier work; primary_rays =
+ * n, nodes_visited = node records the query read, prims_tested = intersection
+ * tests, ms = device time of the launch.  Unknown flag bits, or a NULL dev_rays
+ * / dev_hits with n > 0: RT_E_INVALID.  n == 0: RT_OK, nothing launched.  No
+ * scene: RT_E_NOSCENE.  Reads scene state only: it never changes a frame; a
+ * multi-device handle answers from devices[0]. */
+enum { RT_SWEEP_ENTRY_ONLY = 1u, RT_SWEEP_SKIP_SELF = 2u };
+int rt_sweep_spheres(rt_renderer* r, const void* dev_rays, const void* dev_radii, float radius, uint32_t n,
+                     uint32_t flags, void* dev_hits, void* stream, rt_stats* stats);
+/* A one-cast sweep with tmin = 0 that waits for the answer, like rt_pick.
+ * hit_out as dev_hits above; point_out (may be NULL) = origin + t * dir, the
+ * ball's centre at contact (at a miss: at tmax).  flags as above. */
+int rt_sweep_at(rt_renderer* r, const float origin[3], const float dir[3], float radius, float tmax,
+                uint32_t flags, rt_hit* hit_out, float point_out[3]);
+/* rt_pick's ray (Camera::getRay, tmin = 0, tmax = +inf) as a one-cast sweep of
+ * radius `radius`, no flags: a cursor of finite size.  radius = 0 is rt_pick.
+ * Waits for the answer. */
+int rt_pick_thick(rt_renderer* r, float u, float v, float radius, rt_hit* hit_out, float point_out[3]);
 
 /* ---- first-hit G-buffer --------------------------------------------------- */
 /* The per-pixel geometry of the frame the current size and camera would

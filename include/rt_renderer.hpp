@@ -212,6 +212,29 @@ public:
         check(rt_closest_at(r_, point, max_dist, k, near, &count), r_);
         return count;
     }
+    // the first sphere a ball of radius R touches while its centre moves along
+    // each ray (rt_sweep_spheres): n rt_ray and n radii (or null: every cast
+    // uses `radius`) -> n rt_hit, all in device memory; `dir` of unit length;
+    // flags RT_SWEEP_ENTRY_ONLY | RT_SWEEP_SKIP_SELF
+    void sweepSpheres(const void* dev_rays, uint32_t n, float radius, void* dev_hits,
+                      const void* dev_radii = nullptr, uint32_t flags = 0, void* stream = nullptr,
+                      rt_stats* stats = nullptr) {
+        check(rt_sweep_spheres(r_, dev_rays, dev_radii, radius, n, flags, dev_hits, stream, stats), r_);
+    }
+    // one cast from `origin` along the unit `dir` up to tmax, e.g. a time of
+    // impact (rt_sweep_at); point (may be null): the ball's centre at contact
+    rt_hit sweepAt(const float origin[3], const float dir[3], float radius, float tmax, uint32_t flags = 0,
+                   float point[3] = nullptr) {
+        rt_hit h{};
+        check(rt_sweep_at(r_, origin, dir, radius, tmax, flags, &h, point), r_);
+        return h;
+    }
+    // pick() with a cursor of finite radius (rt_pick_thick)
+    rt_hit pickThick(float u, float v, float radius, float point[3] = nullptr) {
+        rt_hit h{};
+        check(rt_pick_thick(r_, u, v, radius, &h, point), r_);
+        return h;
+    }
     // first-hit G-buffer of the current camera (rt_render_gbuffer): W*H rt_hit,
     // float[4] normals and packed RGBA8 albedo in device memory, each optional
     void renderGBuffer(void* dev_hits, void* dev_normals = nullptr, void* dev_albedo = nullptr,

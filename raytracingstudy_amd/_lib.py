@@ -61,6 +61,8 @@ RT_OVERLAP_MORE = 0x80000000  # in a count word: the accepted set is larger than
 RT_OVERLAP_SKIP_SELF = 1  # rt_query_overlaps flag: probe i does not report sphere index i
 RT_CLOSEST_MAX = 16       # rt_query_closest / rt_closest_at: the largest k
 RT_CLOSEST_SKIP_SELF = 1  # rt_query_closest flag: probe i leaves sphere index i out
+RT_SWEEP_ENTRY_ONLY = 1   # rt_sweep_spheres flag: only the near root counts
+RT_SWEEP_SKIP_SELF = 2    # rt_sweep_spheres flag: cast i leaves sphere index i out
 
 _f3 = ctypes.c_float * 3
 
@@ -266,6 +268,9 @@ SIGNATURES = {
     "rt_overlaps_at": (_int, [_P, _fp, ctypes.c_float, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "rt_query_closest": (_int, [_P, _P, _u32, _u32, _u32, _P, _P, _P, ctypes.POINTER(RtStats)]),
     "rt_closest_at": (_int, [_P, _fp, ctypes.c_float, _u32, ctypes.POINTER(RtNear), ctypes.POINTER(_u32)]),
+    "rt_sweep_spheres": (_int, [_P, _P, _P, ctypes.c_float, _u32, _u32, _P, _P, ctypes.POINTER(RtStats)]),
+    "rt_sweep_at": (_int, [_P, _fp, _fp, ctypes.c_float, ctypes.c_float, _u32, ctypes.POINTER(RtHit), _fp]),
+    "rt_pick_thick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
     "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),

@@ -73,16 +73,6 @@ struct ClosestSet {
     }
 };
 
-// A child mask (bit c: child c, x = 1, y = 2, z = 4) in visiting order: bit j
-// is child j ^ near, so that ctz walks the children nearest octant first.
-// Three conditional swaps, of bits, pairs and nibbles.
-__device__ __forceinline__ uint32_t in_order(uint32_t m, uint32_t near) {
-    m = (near & 1u) ? ((m & 0x55u) << 1) | ((m >> 1) & 0x55u) : m;
-    m = (near & 2u) ? ((m & 0x33u) << 2) | ((m >> 2) & 0x33u) : m;
-    m = (near & 4u) ? ((m & 0x0Fu) << 4) | ((m >> 4) & 0x0Fu) : m;
-    return m;
-}
-
 // For the cell at corner l (finest-grid units) and half-size `half`: the
 // octant of the probe's grid coordinates g against its mid planes, and the
 // children the box meets, in visiting order.  rt_overlap.hip's children_met

@@ -6,7 +6,7 @@
 //   rt_frame.cpp  per-frame preparation and launch (do_render's steps: it plans a
 //                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
-//   rt_queries.cpp    ray, multi-hit, overlap and closest-sphere queries, picking, the G-buffer
+//   rt_queries.cpp    ray, multi-hit, overlap, closest-sphere and swept-sphere queries, picking, the G-buffer
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "rt_closest_math.h"
 #include "rt_overlap_math.h"
 #include "rt_params.h"
+#include "rt_sweep_math.h"
 #include "scene_build.h"
 
 struct ncclComm;  // <rccl/rccl.h>'s ncclComm_t is a pointer to it; only rt_multi.cpp includes that
@@ -69,6 +70,12 @@ hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices,
 hipError_t launch_closest(const FrameArgs& a, const void* probes, void* near, void* counts, uint32_t n,
                           uint32_t k, bool skip_self, float slack_m, unsigned long long* counters,
                           hipStream_t st);
+// rt_sweep.hip: n casts (rt_ray, with radii[i] or, radii null, `radius`) -> n rt_hit: the first sphere
+// each moving ball touches by (t, sphere index) against a.sc; slack_m: sweep_slack_m of the root box;
+// counters != null: a stats launch
+hipError_t launch_sweep(const FrameArgs& a, const void* rays, const void* radii, float radius, void* hits,
+                        uint32_t n, bool entry_only, bool skip_self, float slack_m,
+                        unsigned long long* counters, hipStream_t st);
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
@@ -268,6 +275,8 @@ struct QueryScratch {
     DevBuf<uint32_t> overlap_count;  // and the count word
     DevBuf<uint2> near;              // rt_closest_at: up to RT_CLOSEST_MAX rt_near
     DevBuf<uint32_t> near_count;     // and the count
+    DevBuf<float4> cast;             // rt_sweep_at, rt_pick_thick: one cast's ray,
+    DevBuf<uint2> cast_hit;          // and its hit
     void release() {
         counters.release();
         ray.release();
@@ -279,6 +288,8 @@ struct QueryScratch {
         overlap_count.release();
         near.release();
         near_count.release();
+        cast.release();
+        cast_hit.release();
     }
 };
 

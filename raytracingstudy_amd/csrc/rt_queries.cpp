@@ -1,6 +1,6 @@
 // rt_queries.cpp — the calls that read a scene without rendering a frame
-// (DESIGN.md 5.7): ray, multi-hit, sphere-overlap and closest-sphere queries,
-// their single-item wrappers, the first-hit G-buffer.  The reference has none
+// (DESIGN.md 5.7): ray, multi-hit, sphere-overlap, closest-sphere and
+// swept-sphere queries, their single-item wrappers, the first-hit G-buffer.  The reference has none
 // (Octree::traverse is a stub, include/octree.h:19-21; its render kernel
 // writes one colour per pixel, src/renderer.cu:57-82).  A query reads scene
 // (the G-buffer: and camera) state only: it takes no frame id, leaves the
@@ -94,10 +94,35 @@ void pick_ray(const rt_renderer* r, float u, float v, float4 ray[2]) {
     ray[1] = make_float4(wx, wy, wz, INFINITY);
 }
 
+// One cast (rt_sweep_at, rt_pick_thick; the caller checked its arguments):
+// uploads the ray, sweeps it on the handle's own stream and waits.  hit_out as
+// rt_sweep_spheres writes it; point_out (may be null) = origin + t * dir.
+int sweep_one(rt_renderer* r, const float4 ray[2], float radius, uint32_t flags, rt_hit* hit_out,
+              float point_out[3]) {
+    int st;
+    if ((st = set_device(r))) return st;
+    if ((st = ensure(r, r->q.cast, 2)) || (st = ensure(r, r->q.cast_hit, 1))) return st;
+    hipStream_t hs = own_stream(r);
+    if ((st = order_after_last(r, hs))) return st;
+    RT_HIP(r, hipMemcpyAsync(r->q.cast.p, ray, 2 * sizeof(float4), hipMemcpyHostToDevice, hs));
+    if ((st = rt_sweep_spheres(r, r->q.cast.p, nullptr, radius, 1, flags, r->q.cast_hit.p, hs, nullptr)))
+        return st;
+    uint2 h;
+    RT_HIP(r, hipMemcpyAsync(&h, r->q.cast_hit.p, sizeof(h), hipMemcpyDeviceToHost, hs));
+    RT_HIP(r, hipStreamSynchronize(hs));
+    memcpy(&hit_out->t, &h.x, sizeof(float));
+    hit_out->sphere = h.y;
+    if (point_out) {
+        const float o[3] = {ray[0].x, ray[0].y, ray[0].z}, d[3] = {ray[1].x, ray[1].y, ray[1].z};
+        for (int i = 0; i < 3; ++i) point_out[i] = o[i] + hit_out->t * d[i];
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 // The four single-item wrappers below (rt_pick, rt_pick_multi, rt_overlaps_at,
-// rt_closest_at) stay plain functions: their scratch buffers and copies back
+// rt_closest_at; the two one-cast calls share sweep_one above) stay plain functions: their scratch buffers and copies back
 // differ in number and type, so a shared helper could hold only "order, upload
 // one record" (three lines of each), would need the rest passed in as two
 // callbacks, and would be no shorter than what it replaces.
@@ -300,6 +325,48 @@ int rt_closest_at(rt_renderer* r, const float point[3], float max_dist, uint32_t
     }
     if (count_out) *count_out = count;
     return RT_OK;
+}
+
+// Swept-sphere queries: the first scene sphere a ball of
+// radius R touches while its centre moves along each ray.
+int rt_sweep_spheres(rt_renderer* r, const void* dev_rays, const void* dev_radii, float radius, uint32_t n,
+                     uint32_t flags, void* dev_hits, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_sweep_spheres: null handle");
+    if (flags & ~static_cast<uint32_t>(RT_SWEEP_ENTRY_ONLY | RT_SWEEP_SKIP_SELF))
+        return fail(r, RT_E_INVALID, "rt_sweep_spheres: unknown flag bits");
+    if (n > 0 && (!dev_rays || !dev_hits)) return fail(r, RT_E_INVALID, "rt_sweep_spheres: null buffer");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_sweep_spheres: no scene (rt_set_scene first)");
+    if (n == 0) return nothing_queried(stats);
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    const float slack_m = sweep_slack_m(r->info.root_min, r->info.root_max);
+    st = query_launch(r, "rt_sweep_spheres", hs, stats, [&](unsigned long long* ctr) {
+        return launch_sweep(a, dev_rays, dev_radii, radius, dev_hits, n, (flags & RT_SWEEP_ENTRY_ONLY) != 0,
+                            (flags & RT_SWEEP_SKIP_SELF) != 0, slack_m, ctr, hs);
+    });
+    if (!st && stats) stats->primary_rays = n;
+    return st;
+}
+
+int rt_sweep_at(rt_renderer* r, const float origin[3], const float dir[3], float radius, float tmax,
+                uint32_t flags, rt_hit* hit_out, float point_out[3]) {
+    if (!r || !origin || !dir || !hit_out) return fail(r, RT_E_INVALID, "rt_sweep_at: null argument");
+    if (flags & ~static_cast<uint32_t>(RT_SWEEP_ENTRY_ONLY | RT_SWEEP_SKIP_SELF))
+        return fail(r, RT_E_INVALID, "rt_sweep_at: unknown flag bits");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_sweep_at: no scene (rt_set_scene first)");
+    const float4 ray[2] = {make_float4(origin[0], origin[1], origin[2], 0.0f),
+                           make_float4(dir[0], dir[1], dir[2], tmax)};
+    return sweep_one(r, ray, radius, flags, hit_out, point_out);
+}
+
+int rt_pick_thick(rt_renderer* r, float u, float v, float radius, rt_hit* hit_out, float point_out[3]) {
+    if (!r || !hit_out) return fail(r, RT_E_INVALID, "rt_pick_thick: null argument");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_pick_thick: no scene (rt_set_scene first)");
+    float4 ray[2];
+    pick_ray(r, u, v, ray);
+    return sweep_one(r, ray, radius, 0, hit_out, point_out);
 }
 
 // First-hit G-buffer of the current camera: no

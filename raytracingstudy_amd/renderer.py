@@ -564,6 +564,67 @@ class KernelRenderer:
         dist, sphere = _split_pairs(np.frombuffer(near, np.int32).reshape(-1, 2)[:k])
         return int(cnt.value), dist, sphere
 
+    # -- swept-sphere queries (rt_sweep_spheres / rt_sweep_at / rt_pick_thick) ------
+    def sweep_spheres_device(self, rays_ptr: int, n: int, hits_ptr: int, radius: float = 0.0,
+                             radii_ptr: Optional[int] = None, entry_only: bool = False,
+                             skip_self: bool = False, stream: Optional[int] = None,
+                             stats: bool = False) -> Optional[RtStats]:
+        """rt_sweep_spheres on buffers already on the GPU: n rt_ray at rays_ptr, each
+        the path of the centre of a ball of radius radii_ptr[i] (n floats; None:
+        `radius` for every cast) -> n rt_hit at hits_ptr: the first sphere the
+        ball touches by (t, sphere index), or {tmax, RT_NO_HIT}.  Asynchronous on
+        `stream` (None: the renderer's own) unless stats."""
+        st, st_arg = _stats_arg(stats)
+        flags = (_lib.RT_SWEEP_ENTRY_ONLY if entry_only else 0) | (_lib.RT_SWEEP_SKIP_SELF if skip_self else 0)
+        check(self._lib.rt_sweep_spheres(self._h, _ptr(rays_ptr), _ptr(radii_ptr), float(radius), int(n),
+                                         flags, _ptr(hits_ptr), _ptr(stream), st_arg), self._h)
+        return st
+
+    def sweep_spheres(self, rays, radius, entry_only: bool = False, skip_self: bool = False,
+                      stats: bool = False):
+        """The first scene sphere a ball touches while its centre moves along each
+        ray of a host (n, 8) float32 array in rt_ray layout (`dir` of unit
+        length); `radius` is a scalar or an (n,) array.  Uploads, runs
+        rt_sweep_spheres, and returns (t (n,) float32, sphere (n,) uint32[,
+        RtStats]).  A miss has t = the cast's tmax and sphere = RT_NO_HIT."""
+        ra = _records(rays, 8, "rays", "rt_ray")
+        d_radii = None
+        if np.ndim(radius) != 0:
+            import torch
+            rr = np.array(radius, np.float32)
+            if rr.shape != (len(ra),):
+                raise ValueError("radius must be a scalar or an (n,) float32 array, one per ray")
+            # (on torch's stream, like _batch's upload, whose synchronize covers it)
+            d_radii = torch.from_numpy(rr).to(torch.device("cuda", self.multi_info()["devices"][0]))
+        st, (hits,) = self._batch(ra, [(2,)], lambda d_rays, d_hits: self.sweep_spheres_device(
+            d_rays, len(ra), d_hits, 0.0 if d_radii is not None else float(radius),
+            d_radii.data_ptr() if d_radii is not None and len(ra) else None, entry_only, skip_self, None, stats))
+        t, sphere = _split_pairs(hits)
+        return (t, sphere, st) if stats else (t, sphere)
+
+    def sweep_at(self, origin, direction, radius: float, tmax: float = float("inf"),
+                 entry_only: bool = False):
+        """rt_sweep_at: one ball of `radius` from `origin` along the unit `direction`
+        up to tmax (tmin = 0), e.g. a time of impact -> (hit: bool, t, sphere,
+        point (3,) float32: the ball's centre at contact)."""
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+        d = np.ascontiguousarray(np.asarray(direction, np.float32).reshape(3))
+        h = _lib.RtHit()
+        pt = np.zeros(3, np.float32)
+        check(self._lib.rt_sweep_at(self._h, _fptr(o), _fptr(d), float(radius), float(tmax),
+                                    _lib.RT_SWEEP_ENTRY_ONLY if entry_only else 0, ctypes.byref(h),
+                                    _fptr(pt)), self._h)
+        return h.sphere != _lib.RT_NO_HIT, float(h.t), int(h.sphere), pt
+
+    def pick_thick(self, u: float, v: float, radius: float):
+        """rt_pick_thick: pick() with a cursor of finite `radius` (world units) ->
+        (hit: bool, t, sphere, point (3,) float32: the cursor ball's centre at contact)."""
+        h = _lib.RtHit()
+        pt = np.zeros(3, np.float32)
+        check(self._lib.rt_pick_thick(self._h, float(u), float(v), float(radius), ctypes.byref(h), _fptr(pt)),
+              self._h)
+        return h.sphere != _lib.RT_NO_HIT, float(h.t), int(h.sphere), pt
+
     # -- first-hit G-buffer (rt_render_gbuffer) -----------------------------------
     def render_gbuffer_device(self, hits_ptr: Optional[int] = None, normals_ptr: Optional[int] = None,
                               albedo_ptr: Optional[int] = None, stream: Optional[int] = None,
