@@ -4,18 +4,18 @@
 // the probe's search radius.  The reference has no counterpart
 // (Octree::traverse is a stub, include/octree.h:19-21).
 //
-// One probe per lane in rt_overlap.hip's box-guided depth-first descent of the
-// octree records, with two differences: the box is the grown box of the
-// lane's bound (rt_closest_math.h), which shrinks as answers come in, and a
-// node's children are visited nearest octant first, so that the first leaves
-// reached are near the probe and the bound is small early.
+// One probe per lane in the guided descent of the octree records
+// (rt_descent.h).  This kernel adds its guide, ShrinkingBoxGuide (a cell is
+// visited iff it meets the grown box of the lane's bound, rt_closest_math.h,
+// which shrinks as answers come in; a node's children are visited nearest
+// octant first, so that the first leaves reached are near the probe and the
+// bound is small early), and its leaf step (the key, and the K nearest
+// accepted spheres in ClosestSet).
 // Compiled like rt_query.hip (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 
 #include "rt_closest_math.h"
-#include "rt_params.h"
-#include "rt_query_common.h"
-#include "rt_walk.h"
+#include "rt_descent.h"
 
 namespace rtamd {
 
@@ -77,10 +77,9 @@ struct ClosestSet {
 // octant of the probe's grid coordinates g against its mid planes, and the
 // children the box meets, in visiting order.  rt_overlap.hip's children_met
 // (per axis the lower half unless lo >= mid, the upper unless hi < mid) with
-// every prune written so that a NaN comparison visits.
-struct ChildOrder {
-    uint32_t near, met;
-};
+// every prune written so that a NaN comparison visits.  The two stay two: one
+// form for both would change what a NaN corner does in one of the kernels,
+// and its comparisons with it.
 __device__ __forceinline__ ChildOrder children_in_order(const ClosestBox& b, const float g[3], uint32_t l0,
                                                         uint32_t l1, uint32_t l2, uint32_t half) {
     const float m0 = static_cast<float>(l0 + half);  // integers <= 2^16: exact
@@ -95,12 +94,37 @@ __device__ __forceinline__ ChildOrder children_in_order(const ClosestBox& b, con
     return o;
 }
 
+// The guide: the grown box of the lane's bound, rebuilt when a leaf lowered
+// the K-th key; the children nearest octant first.
+struct ShrinkingBoxGuide {
+    enum { kReprune = 1 };
+    float4 p;
+    float g[3];  // the probe's grid coordinates: they only order the children
+    ClosestBox b;
+    float bound;  // the bound the box was built for: the radius, then the K-th key
+    const SceneArgs& S;
+    float slack_m;
+    const float& kth;  // the lane's bound now (ClosestSet::key[K - 1])
+    __device__ __forceinline__ bool root_met() const {
+        const bool out_of_root = b.lo[0] >= S.G || b.lo[1] >= S.G || b.lo[2] >= S.G || b.hi[0] < 0.0f ||
+                                 b.hi[1] < 0.0f || b.hi[2] < 0.0f;
+        return !out_of_root;
+    }
+    __device__ __forceinline__ ChildOrder children(uint32_t l0, uint32_t l1, uint32_t l2, uint32_t half) const {
+        return children_in_order(b, g, l0, l1, l2, half);
+    }
+    __device__ __forceinline__ bool shrank() {
+        if (!(kth < bound)) return false;
+        bound = kth;
+        b = closest_box(p.x, p.y, p.z, bound, S.rmin, S.scale, slack_m);
+        return true;
+    }
+};
+
 // One probe per lane, 256-thread blocks, the K-entry buffer in registers (K is
 // the caller's k rounded up to a compiled size).  A probe is one coalesced
 // dwordx4 load.  FrameArgs leads the argument block as in rt_query.hip.  The
-// dynamic LDS is the per-lane descent stack, [level][thread]: level d holds
-// the node at depth d while the lane is below it: {first child slot, valid |
-// leaf << 8 | children still to visit, in visiting order << 16}.
+// dynamic LDS is the descent's per-lane stack (rt_descent.h).
 template <int K, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) closest_kernel(FrameArgs a, ClosestArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -115,93 +139,26 @@ __global__ void __launch_bounds__(kBlockThreads) closest_kernel(FrameArgs a, Clo
         const uint32_t self = q.skip_self ? i : kNoHit;
         const float4* __restrict__ prim_sp = S.prim_sp;
         const uint32_t* __restrict__ prim_idx = S.prim_idx;
-        // A leaf's spheres in list order, kLeafChunk loads in flight; a slot
-        // past the leaf's end reads the next leaf or the kPrimPad tail (in
-        // bounds) and is never tested.  prim_idx is read only for a sphere
-        // whose key passes the bound (closed: an equal key with a smaller
-        // index still gets in).
-        auto leaf = [&](uint32_t off, uint32_t cnt) {
-            static_assert(kLeafChunk <= static_cast<int>(kPrimPad) + 1, "leaf loads may run past a leaf");
-            for (uint32_t j = 0; j < cnt; j += kLeafChunk) {
-                float4 sv[kLeafChunk];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) sv[s] = prim_sp[off + j + s];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) {
-                    if (j + s < cnt) {
-                        if (kStats) n_prims += 1;
-                        const float kc = closest_key(p.x, p.y, p.z, sv[s].x, sv[s].y, sv[s].z, sv[s].w);
-                        if (kc <= set.key[K - 1]) {
-                            const uint32_t ci = prim_idx[off + j + s];
-                            if (ci != self) set.offer(kc, ci);
-                        }
-                    }
-                }
+        // prim_idx is read only for a sphere whose key passes the bound
+        // (closed: an equal key with a smaller index still gets in)
+        auto test = [&](const float4& s, uint32_t slot) {
+            const float kc = closest_key(p.x, p.y, p.z, s.x, s.y, s.z, s.w);
+            if (kc <= set.key[K - 1]) {
+                const uint32_t ci = prim_idx[slot];
+                if (ci != self) set.offer(kc, ci);
             }
         };
+        auto leaf = [&](uint32_t off, uint32_t cnt) { leaf_spheres<kStats>(prim_sp, off, cnt, n_prims, test); };
         if (closest_probe_ok(p.x, p.y, p.z, p.w)) {
-            // the bound the box was built for: the radius, then the K-th key
-            float bound = p.w;
-            ClosestBox b = closest_box(p.x, p.y, p.z, bound, S.rmin, S.scale, q.slack_m);
-            // the probe's grid coordinates: they only order the children
-            const float g[3] = {(p.x - S.rmin[0]) * S.scale[0], (p.y - S.rmin[1]) * S.scale[1],
-                                (p.z - S.rmin[2]) * S.scale[2]};
-            const bool out_of_root = b.lo[0] >= S.G || b.lo[1] >= S.G || b.lo[2] >= S.G || b.hi[0] < 0.0f ||
-                                     b.hi[1] < 0.0f || b.hi[2] < 0.0f;
-            if (!out_of_root) {
-                if (kStats) n_nodes += 1;  // the root record
-                if (S.root_is_leaf) {
-                    if (S.root.y) leaf(S.root.x, S.root.y);  // an empty scene's root holds 0
-                } else {
-                    // the node the lane iterates: its record, depth, corner and
-                    // size, its near octant, and the children still to visit in
-                    // visiting order (a mask that only loses bits)
-                    uint2 node = S.root;
-                    uint32_t depth = 0, l0 = 0, l1 = 0, l2 = 0, size = 1u << S.max_depth;
-                    ChildOrder o = children_in_order(b, g, l0, l1, l2, size >> 1);
-                    uint32_t rem = o.met & in_order(node.y & 0xFFu, o.near);
-                    for (;;) {
-                        if (rem == 0u) {
-                            if (depth == 0u) break;
-                            depth -= 1;
-                            size <<= 1;
-                            l0 &= ~(size - 1u);
-                            l1 &= ~(size - 1u);
-                            l2 &= ~(size - 1u);
-                            node = stk[depth * kBlockThreads];
-                            // the box may have shrunk since this node was left:
-                            // it prunes the siblings queued then
-                            o = children_in_order(b, g, l0, l1, l2, size >> 1);
-                            rem = (node.y >> 16) & o.met;
-                            continue;
-                        }
-                        const uint32_t c = static_cast<uint32_t>(__builtin_ctz(rem)) ^ o.near;
-                        rem &= rem - 1u;
-                        const uint32_t valid = node.y & 0xFFu;
-                        const uint2 rec = S.nodes[node.x + __builtin_popcount(valid & ((1u << c) - 1u))];
-                        if (kStats) n_nodes += 1;
-                        if ((node.y >> 8) & (1u << c)) {
-                            leaf(rec.x, rec.y);
-                            if (set.key[K - 1] < bound) {
-                                bound = set.key[K - 1];
-                                b = closest_box(p.x, p.y, p.z, bound, S.rmin, S.scale, q.slack_m);
-                                rem &= children_in_order(b, g, l0, l1, l2, size >> 1).met;
-                            }
-                        } else if (depth < q.levels) {  // (always: the stack holds every internal depth)
-                            stk[depth * kBlockThreads] = make_uint2(node.x, (node.y & 0xFFFFu) | (rem << 16));
-                            const uint32_t half = size >> 1;
-                            l0 += (c & 1u) ? half : 0u;
-                            l1 += (c & 2u) ? half : 0u;
-                            l2 += (c & 4u) ? half : 0u;
-                            size = half;
-                            depth += 1;
-                            node = rec;
-                            o = children_in_order(b, g, l0, l1, l2, size >> 1);
-                            rem = o.met & in_order(node.y & 0xFFu, o.near);
-                        }
-                    }
-                }
-            }
+            ShrinkingBoxGuide guide = {p,
+                                       {(p.x - S.rmin[0]) * S.scale[0], (p.y - S.rmin[1]) * S.scale[1],
+                                        (p.z - S.rmin[2]) * S.scale[2]},
+                                       closest_box(p.x, p.y, p.z, p.w, S.rmin, S.scale, q.slack_m),
+                                       p.w,
+                                       S,
+                                       q.slack_m,
+                                       set.key[K - 1]};
+            descend<kStats>(S, stk, q.levels, guide, leaf, n_nodes);
         }
         uint2* out = q.near + static_cast<size_t>(i) * q.k;
         uint32_t held = 0;
@@ -242,10 +199,7 @@ hipError_t launch_closest(const FrameArgs& a, const void* probes, void* near, vo
     q.n = n;
     q.k = k;
     q.skip_self = skip_self ? 1u : 0u;
-    // one level per depth that can hold an internal node (SceneArgs::
-    // stack_depth, as rt_overlap.hip: this descent does not enter through the
-    // cell table either)
-    q.levels = a.sc.stack_depth ? a.sc.stack_depth : 1u;
+    q.levels = descent_levels(a.sc);
     q.slack_m = slack_m;
     q.counters = counters;
     const dim3 grid = query_grid(n), block(kBlockThreads);

@@ -1,33 +1,26 @@
 // rt_closest_math.h — the closest-sphere query's arithmetic (rt_query_closest,
 // include/rt.h), free of HIP and of the renderer's state: the
 // probe's validity, the key (the signed distance to a sphere's surface) and the
-// grown box of a bound that guides the descent.  f32 operations in a fixed
-// order (built with -ffp-contract=off like the rest, IEEE sqrtf).
+// slack and the reach of the grown box of a bound that guides the descent
+// (rt_guide_math.h: the box itself).  f32 operations in a fixed order (built
+// with -ffp-contract=off like the rest, IEEE sqrtf).
 // rt_closest.hip runs it per probe on the device, and
 // tests/native/closest_math_dump.cpp prints it for tests/test_closest_cpu.py.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define RT_CLS_HD __host__ __device__
-#else
-#define RT_CLS_HD
-#endif
+#include "rt_guide_math.h"
 
 namespace rtamd {
 
 // A probe takes part iff its centre is finite and R >= 0 (R = -0 and R = +inf
 // included; a NaN R fails the comparison); any other probe has an empty set.
-RT_CLS_HD inline bool closest_probe_ok(float px, float py, float pz, float R) {
-    const float big = 3.402823466e+38f;  // FLT_MAX: !(|x| <= big) <=> x is NaN or infinite
-    return fabsf(px) <= big && fabsf(py) <= big && fabsf(pz) <= big && R >= 0.0f;
+RT_GUIDE_HD inline bool closest_probe_ok(float px, float py, float pz, float R) {
+    return finite_f32(px) && finite_f32(py) && finite_f32(pz) && R >= 0.0f;
 }
 
 // The key of sphere (c, r) for probe point p: sqrtf(d2) - r, the signed
 // distance from p to the sphere's surface (negative inside), every operation
 // one IEEE f32 operation in this order.  A d2 that overflows gives +inf.
-RT_CLS_HD inline float closest_key(float px, float py, float pz, float cx, float cy, float cz, float r) {
+RT_GUIDE_HD inline float closest_key(float px, float py, float pz, float cx, float cy, float cz, float r) {
     const float dx = px - cx;
     const float dy = py - cy;
     const float dz = pz - cz;
@@ -63,40 +56,21 @@ constexpr double kClosestSlackR = 32.0;
 constexpr double kClosestSlackM = 64.0;
 static_assert(kClosestSlackR >= kClosestNeedR + 4.0 && kClosestSlackM >= kClosestNeedM + 4.0,
               "the grown box covers the key's rounding, the grid conversion and its own");
-constexpr double kClosestU = 1.0 / 16777216.0;  // 2^-24
 
 // The scene's part of the slack: kClosestSlackM u M for the effective root box.
 inline float closest_slack_m(const float rmin[3], const float rmax[3]) {
-    double m2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double a = fabs(static_cast<double>(rmin[i])), b = fabs(static_cast<double>(rmax[i]));
-        const double c = a > b ? a : b;
-        m2 += c * c;
-    }
-    return static_cast<float>(kClosestSlackM * kClosestU * sqrt(m2));
+    return static_cast<float>(kClosestSlackM * kGuideU * root_corner_far(rmin, rmax));
 }
 
-// The grown box of (p, max(bound, 0)) in the walk's grid coordinates
-// (SceneArgs::rmin, scale): a cell [l, l + size) of the finest grid is met on
-// an axis unless lo >= l + size or hi < l.  max(., 0): every sphere that
+// The grown box of a bound: the reach is max(bound, 0).  Every sphere that
 // contains p is listed in p's own cell, so a negative bound (the K-th nearest
-// surface is behind p) still has to reach that cell.  Monotone in the bound:
-// a smaller bound's box lies inside a larger one's.
-struct ClosestBox {
-    float lo[3], hi[3];
-};
-RT_CLS_HD inline ClosestBox closest_box(float px, float py, float pz, float bound, const float rmin[3],
+// surface is behind p) still has to reach that cell.  A cell is met on an axis
+// unless lo >= l + size or hi < l (a NaN comparison visits).
+using ClosestBox = GridBox;
+RT_GUIDE_HD inline ClosestBox closest_box(float px, float py, float pz, float bound, const float rmin[3],
                                         const float scale[3], float slack_m) {
-    const float rel = static_cast<float>(1.0 + kClosestSlackR * kClosestU);
-    const float reach = bound > 0.0f ? bound : 0.0f;
-    const float grow = reach * rel + slack_m;
-    const float p[3] = {px, py, pz};
-    ClosestBox b;
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = ((p[i] - grow) - rmin[i]) * scale[i];
-        b.hi[i] = ((p[i] + grow) - rmin[i]) * scale[i];
-    }
-    return b;
+    const float rel = static_cast<float>(1.0 + kClosestSlackR * kGuideU);
+    return grown_box(px, py, pz, bound > 0.0f ? bound : 0.0f, rel, rmin, scale, slack_m);
 }
 
 }  // namespace rtamd

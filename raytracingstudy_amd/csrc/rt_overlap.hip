@@ -3,16 +3,16 @@
 // of the scene spheres it touches, and whether there are more.  The reference
 // has no counterpart (Octree::traverse is a stub, include/octree.h:19-21).
 //
-// One probe per lane in a box-guided depth-first descent of the octree
-// records: a cell is visited iff it meets the probe's grown box
-// (rt_overlap_math.h), a leaf's spheres are tested with the exact predicate.
+// One probe per lane in the guided descent of the octree records
+// (rt_descent.h).  This kernel adds its guide, BoxGuide (a cell is visited iff
+// it meets the probe's grown box, rt_overlap_math.h; the children in index
+// order; the box never changes), and its leaf step (the exact predicate, and
+// the K smallest accepted indices in OverlapSet).
 // Compiled like rt_query.hip (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 
+#include "rt_descent.h"
 #include "rt_overlap_math.h"
-#include "rt_params.h"
-#include "rt_query_common.h"
-#include "rt_walk.h"
 
 namespace rtamd {
 
@@ -33,20 +33,24 @@ constexpr uint32_t kOverlapMore = 0x80000000u;  // RT_OVERLAP_MORE
 // One lane's K smallest accepted sphere indices, ascending, a free slot
 // kNoHit (which sorts after every index).  `more`: a sphere that is not held
 // was turned away from a full buffer, or an entry was pushed out, so the set
-// is larger than K.  Every index below is a compile-time constant once the
-// loops are unrolled: the array is registers, never scratch.
+// is larger than K.  It is a word, not a bool: a bool that lives across the
+// descent is a lane mask, and the compiler lost that mask's initial value for
+// the lanes that skip the descent (a probe beside a root that is a leaf could
+// report MORE with nothing held; profiles/r24/README.md).  Every index below
+// is a compile-time constant once the loops are unrolled: the array is
+// registers, never scratch.
 template <int K>
 struct OverlapSet {
     uint32_t idx[K];
-    bool more;
+    uint32_t more;  // 0 | 1
     __device__ __forceinline__ void clear() {
 #pragma unroll
         for (int i = 0; i < K; ++i) idx[i] = kNoHit;
-        more = false;
+        more = 0u;
     }
     __device__ __forceinline__ void offer(uint32_t ci) {
         if (ci > idx[K - 1]) {  // (the last slot is taken, or ci could not exceed it)
-            more = true;
+            more = 1u;
             return;
         }
         uint32_t pos = 0;  // entries that sort before the candidate
@@ -57,7 +61,7 @@ struct OverlapSet {
             held |= idx[i] == ci;
         }
         if (held) return;  // met again in another leaf
-        more |= idx[K - 1] != kNoHit;
+        more |= idx[K - 1] != kNoHit ? 1u : 0u;
 #pragma unroll
         for (int i = K - 1; i >= 0; --i) {
             const bool below = static_cast<uint32_t>(i) > pos;  // shifts down one slot
@@ -82,13 +86,26 @@ __device__ __forceinline__ uint32_t children_met(const OverlapBox& b, uint32_t l
     return x & y & z;
 }
 
+// The guide: the probe's grown box, the same for the whole descent (the set
+// only grows), the children in index order.
+struct BoxGuide {
+    enum { kReprune = 0 };  // the mask a pop finds is still right
+    OverlapBox b;
+    float G;
+    __device__ __forceinline__ bool root_met() const {
+        return b.lo[0] < G && b.lo[1] < G && b.lo[2] < G && b.hi[0] >= 0.0f && b.hi[1] >= 0.0f && b.hi[2] >= 0.0f;
+    }
+    __device__ __forceinline__ ChildOrder children(uint32_t l0, uint32_t l1, uint32_t l2, uint32_t half) const {
+        return {0u, children_met(b, l0, l1, l2, half)};
+    }
+    __device__ __forceinline__ bool shrank() const { return false; }
+};
+
 // One probe per lane, 256-thread blocks, the K-entry buffer in registers (K is
 // the caller's k rounded up to a compiled size).  A probe is one coalesced
 // dwordx4 load.  FrameArgs leads the argument block as in rt_query.hip.  The
-// dynamic LDS is the per-lane descent stack, [level][thread]: level d holds
-// the node at depth d while the lane is below it: {first child slot, valid |
-// leaf << 8 | children still to visit << 16}.
-// (rt_query_common.h holds what is shared; the stack and the flush stay here: a helper moves registers in the stats instances)
+// dynamic LDS is the descent's per-lane stack (rt_descent.h).
+// (rt_query_common.h: the stack's declaration and the flush stay here: a helper moves registers in the stats instances)
 template <int K, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, OverlapArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -103,75 +120,17 @@ __global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, Ove
         const uint32_t self = q.skip_self ? i : kNoHit;
         const float4* __restrict__ prim_sp = S.prim_sp;
         const uint32_t* __restrict__ prim_idx = S.prim_idx;
-        // A leaf's spheres in list order, kLeafChunk loads in flight; a slot
-        // past the leaf's end reads the next leaf or the kPrimPad tail (in
-        // bounds) and is never tested.  prim_idx is read for accepted ones only.
-        auto leaf = [&](uint32_t off, uint32_t cnt) {
-            static_assert(kLeafChunk <= static_cast<int>(kPrimPad) + 1, "leaf loads may run past a leaf");
-            for (uint32_t j = 0; j < cnt; j += kLeafChunk) {
-                float4 sv[kLeafChunk];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) sv[s] = prim_sp[off + j + s];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) {
-                    if (j + s < cnt) {
-                        if (kStats) n_prims += 1;
-                        if (overlap_accepts(p.x, p.y, p.z, p.w, sv[s].x, sv[s].y, sv[s].z, sv[s].w)) {
-                            const uint32_t ci = prim_idx[off + j + s];
-                            if (ci != self) set.offer(ci);
-                        }
-                    }
-                }
+        // prim_idx is read for accepted spheres only
+        auto test = [&](const float4& s, uint32_t slot) {
+            if (overlap_accepts(p.x, p.y, p.z, p.w, s.x, s.y, s.z, s.w)) {
+                const uint32_t ci = prim_idx[slot];
+                if (ci != self) set.offer(ci);
             }
         };
+        auto leaf = [&](uint32_t off, uint32_t cnt) { leaf_spheres<kStats>(prim_sp, off, cnt, n_prims, test); };
         if (overlap_probe_ok(p.x, p.y, p.z, p.w)) {
-            const OverlapBox b = overlap_box(p.x, p.y, p.z, p.w, S.rmin, S.scale, q.slack_m);
-            const bool in_root = b.lo[0] < S.G && b.lo[1] < S.G && b.lo[2] < S.G && b.hi[0] >= 0.0f &&
-                                 b.hi[1] >= 0.0f && b.hi[2] >= 0.0f;
-            if (in_root) {
-                if (kStats) n_nodes += 1;  // the root record
-                if (S.root_is_leaf) {
-                    if (S.root.y) leaf(S.root.x, S.root.y);  // an empty scene's root holds 0
-                } else {
-                    // the node the lane iterates: its record, depth, corner and
-                    // size, and the children still to visit (a mask that only
-                    // loses bits: no child is visited twice)
-                    uint2 node = S.root;
-                    uint32_t depth = 0, l0 = 0, l1 = 0, l2 = 0, size = 1u << S.max_depth;
-                    uint32_t rem = children_met(b, l0, l1, l2, size >> 1) & node.y & 0xFFu;
-                    for (;;) {
-                        if (rem == 0u) {
-                            if (depth == 0u) break;
-                            depth -= 1;
-                            size <<= 1;
-                            l0 &= ~(size - 1u);
-                            l1 &= ~(size - 1u);
-                            l2 &= ~(size - 1u);
-                            node = stk[depth * kBlockThreads];
-                            rem = node.y >> 16;
-                            continue;
-                        }
-                        const uint32_t c = static_cast<uint32_t>(__builtin_ctz(rem));
-                        rem &= rem - 1u;
-                        const uint32_t valid = node.y & 0xFFu;
-                        const uint2 rec = S.nodes[node.x + __builtin_popcount(valid & ((1u << c) - 1u))];
-                        if (kStats) n_nodes += 1;
-                        if ((node.y >> 8) & (1u << c)) {
-                            leaf(rec.x, rec.y);
-                        } else if (depth < q.levels) {  // (always: the stack holds every internal depth)
-                            stk[depth * kBlockThreads] = make_uint2(node.x, (node.y & 0xFFFFu) | (rem << 16));
-                            const uint32_t half = size >> 1;
-                            l0 += (c & 1u) ? half : 0u;
-                            l1 += (c & 2u) ? half : 0u;
-                            l2 += (c & 4u) ? half : 0u;
-                            size = half;
-                            depth += 1;
-                            node = rec;
-                            rem = children_met(b, l0, l1, l2, size >> 1) & node.y & 0xFFu;
-                        }
-                    }
-                }
-            }
+            BoxGuide guide = {overlap_box(p.x, p.y, p.z, p.w, S.rmin, S.scale, q.slack_m), S.G};
+            descend<kStats>(S, stk, q.levels, guide, leaf, n_nodes);
         }
         uint32_t* out = q.indices + static_cast<size_t>(i) * q.k;
         uint32_t held = 0;
@@ -181,7 +140,7 @@ __global__ void __launch_bounds__(kBlockThreads) overlap_kernel(FrameArgs a, Ove
             if (static_cast<uint32_t>(s) < q.k) out[s] = set.idx[s];
         }
         if (q.counts) {
-            const bool more = set.more || held > q.k;
+            const bool more = set.more != 0u || held > q.k;
             q.counts[i] = min(held, q.k) | (more ? kOverlapMore : 0u);
         }
     }
@@ -213,10 +172,7 @@ hipError_t launch_overlap(const FrameArgs& a, const void* probes, void* indices,
     q.n = n;
     q.k = k;
     q.skip_self = skip_self ? 1u : 0u;
-    // one level per depth that can hold an internal node, from the deepest
-    // leaf itself (SceneArgs::stack_depth), not from stack_levels(): that one
-    // shrinks with the cell table, which this descent does not enter through
-    q.levels = a.sc.stack_depth ? a.sc.stack_depth : 1u;
+    q.levels = descent_levels(a.sc);
     q.slack_m = slack_m;
     q.counters = counters;
     const dim3 grid = query_grid(n), block(kBlockThreads);

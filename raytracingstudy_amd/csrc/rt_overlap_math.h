@@ -1,31 +1,24 @@
 // rt_overlap_math.h — the sphere-overlap query's arithmetic (rt_query_overlaps,
 // include/rt.h), free of HIP and of the renderer's state: the
-// acceptance predicate and the grown box that guides the descent.  f32
-// operations in a fixed order (built with -ffp-contract=off like the rest).
+// acceptance predicate and the slack of the grown box that guides the descent
+// (rt_guide_math.h: the box itself).  f32 operations in a fixed order (built
+// with -ffp-contract=off like the rest).
 // rt_overlap.hip runs it per probe on the device, and
 // tests/native/overlap_math_dump.cpp prints it for tests/test_overlap_cpu.py.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define RT_OVL_HD __host__ __device__
-#else
-#define RT_OVL_HD
-#endif
+#include "rt_guide_math.h"
 
 namespace rtamd {
 
 // A probe takes part iff its four components are finite and R >= 0 (R = -0
 // included); any other probe has an empty set.
-RT_OVL_HD inline bool overlap_probe_ok(float px, float py, float pz, float R) {
-    const float big = 3.402823466e+38f;  // FLT_MAX: !(|x| <= big) <=> x is NaN or infinite
-    return fabsf(px) <= big && fabsf(py) <= big && fabsf(pz) <= big && R >= 0.0f && R <= big;
+RT_GUIDE_HD inline bool overlap_probe_ok(float px, float py, float pz, float R) {
+    return finite_f32(px) && finite_f32(py) && finite_f32(pz) && R >= 0.0f && R <= kF32Max;
 }
 
 // The acceptance predicate: probe (p, R) touches sphere (c, r) iff
 // d2 <= s * s, closed, every operation one IEEE f32 operation in this order.
-RT_OVL_HD inline bool overlap_accepts(float px, float py, float pz, float R, float cx, float cy,
+RT_GUIDE_HD inline bool overlap_accepts(float px, float py, float pz, float R, float cx, float cy,
                                       float cz, float r) {
     const float dx = px - cx;
     const float dy = py - cy;
@@ -59,36 +52,18 @@ constexpr double kOverlapSlackR = 32.0;
 constexpr double kOverlapSlackM = 64.0;
 static_assert(kOverlapSlackR >= kOverlapNeedR + 4.0 && kOverlapSlackM >= kOverlapNeedM + 4.0,
               "the grown box covers the predicate's rounding, the grid conversion and its own");
-constexpr double kOverlapU = 1.0 / 16777216.0;  // 2^-24
 
 // The scene's part of the slack: kOverlapSlackM u M for the effective root box.
 inline float overlap_slack_m(const float rmin[3], const float rmax[3]) {
-    double m2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double a = fabs(static_cast<double>(rmin[i])), b = fabs(static_cast<double>(rmax[i]));
-        const double c = a > b ? a : b;
-        m2 += c * c;
-    }
-    return static_cast<float>(kOverlapSlackM * kOverlapU * sqrt(m2));
+    return static_cast<float>(kOverlapSlackM * kGuideU * root_corner_far(rmin, rmax));
 }
 
-// The grown box of probe (p, R) in the walk's grid coordinates (SceneArgs::
-// rmin, scale): a cell [l, l + size) of the finest grid is met on an axis iff
-// lo < l + size and hi >= l (the descent's mid-plane rule, level by level).
-struct OverlapBox {
-    float lo[3], hi[3];
-};
-RT_OVL_HD inline OverlapBox overlap_box(float px, float py, float pz, float R, const float rmin[3],
+// The grown box of probe (p, R): the reach is R itself.
+using OverlapBox = GridBox;
+RT_GUIDE_HD inline OverlapBox overlap_box(float px, float py, float pz, float R, const float rmin[3],
                                         const float scale[3], float slack_m) {
-    const float rel = static_cast<float>(1.0 + kOverlapSlackR * kOverlapU);
-    const float grow = R * rel + slack_m;
-    const float p[3] = {px, py, pz};
-    OverlapBox b;
-    for (int i = 0; i < 3; ++i) {
-        b.lo[i] = ((p[i] - grow) - rmin[i]) * scale[i];
-        b.hi[i] = ((p[i] + grow) - rmin[i]) * scale[i];
-    }
-    return b;
+    const float rel = static_cast<float>(1.0 + kOverlapSlackR * kGuideU);
+    return grown_box(px, py, pz, R, rel, rmin, scale, slack_m);
 }
 
 }  // namespace rtamd

@@ -1,7 +1,8 @@
 // rt_query_common.h — what the query units (rt_query.hip, rt_multihit.hip,
 // rt_overlap.hip, rt_closest.hip, rt_sweep.hip, rt_gbuffer.hip) share: the stats launches' wave
 // sum and the visiting-order permutation of a child mask on the device, and the launchers' grid,
-// stack size and k dispatch on the host.
+// stack size and k dispatch on the host.  rt_descent.h holds what the overlap, closest and sweep
+// units share beyond that: their descent, leaf scan and stack levels.
 //
 // Two more things look shared and stay written out in each kernel: the
 // `extern __shared__` stack declaration and the stats flush block.  Behind a
@@ -26,7 +27,8 @@ __device__ __forceinline__ unsigned long long query_wave_sum(unsigned long long 
 
 // A child mask (bit c: child c, x = 1, y = 2, z = 4) in visiting order: bit j
 // is child j ^ near, so that ctz walks the children from `near` outward
-// (rt_closest.hip: the probe's octant; rt_sweep.hip: the direction's signs).
+// (rt_closest.hip: the probe's octant; rt_sweep.hip: the direction's signs;
+// rt_overlap.hip: 0, the index order).
 // Three conditional swaps, of bits, pairs and nibbles.
 __device__ __forceinline__ uint32_t in_order(uint32_t m, uint32_t near) {
     m = (near & 1u) ? ((m & 0x55u) << 1) | ((m >> 1) & 0x55u) : m;

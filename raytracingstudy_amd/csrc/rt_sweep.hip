@@ -4,8 +4,10 @@
 // touches, by (t, sphere index).  The reference has no counterpart
 // (Octree::traverse is a stub, include/octree.h:19-21).
 //
-// One cast per lane in rt_closest.hip's depth-first descent of the octree
-// records, guided by a segment instead of a box: a child is visited iff the
+// One cast per lane in the guided descent of the octree records
+// (rt_descent.h).  This kernel adds its leaf step (the inflated ray-sphere
+// test, and the best (t, index) so far) and its guide, SegmentGuide, a segment
+// where the other two have a box: a child is visited iff the
 // segment tmin < t <= bound meets its cell grown by R and the slack
 // (rt_sweep_math.h: a slab test, so an oblique cast visits a tube of cells and
 // not its bounding box), the bound is the best t so far, and a node's children
@@ -16,10 +18,8 @@
 // Compiled like rt_query.hip (-ffp-contract=off).
 #include <hip/hip_runtime.h>
 
-#include "rt_params.h"
-#include "rt_query_common.h"
+#include "rt_descent.h"
 #include "rt_sweep_math.h"
-#include "rt_walk.h"
 
 namespace rtamd {
 
@@ -58,12 +58,31 @@ __device__ __forceinline__ uint32_t sweep_children(const SweepGuide& sg, float t
     return in_order(m, near);
 }
 
+// The guide: the segment tmin < t <= best_t, which every hit shortens; the
+// children in the order of the direction's signs.
+struct SegmentGuide {
+    enum { kReprune = 1 };
+    SweepGuide sg;
+    float tmin;
+    uint32_t near;
+    float G;
+    float bound;          // the bound the last mask was tested against
+    const float& best_t;  // the lane's bound now
+    __device__ __forceinline__ bool root_met() const {
+        return sweep_meets(sweep_slab(sg, 0, 0.0f, G), sweep_slab(sg, 1, 0.0f, G), sweep_slab(sg, 2, 0.0f, G), tmin,
+                           best_t);
+    }
+    __device__ __forceinline__ ChildOrder children(uint32_t l0, uint32_t l1, uint32_t l2, uint32_t half) {
+        bound = best_t;
+        return {near, sweep_children(sg, tmin, bound, l0, l1, l2, half, near)};
+    }
+    __device__ __forceinline__ bool shrank() const { return best_t < bound; }
+};
+
 // One cast per lane, 256-thread blocks.  A ray is two coalesced dwordx4 loads,
 // a radius a coalesced dword load or the kernel argument, a hit one dwordx2
 // store.  FrameArgs leads the argument block as in rt_query.hip.  The dynamic
-// LDS is the per-lane descent stack, [level][thread]: level d holds the node
-// at depth d while the lane is below it: {first child slot, valid | leaf << 8
-// | children still to visit, in visiting order << 16}.
+// LDS is the descent's per-lane stack (rt_descent.h).
 template <bool kEntryOnly, bool kStats>
 __global__ void __launch_bounds__(kBlockThreads) sweep_kernel(FrameArgs a, SweepArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
@@ -84,36 +103,22 @@ __global__ void __launch_bounds__(kBlockThreads) sweep_kernel(FrameArgs a, Sweep
         const uint32_t self = q.skip_self ? i : kNoHit;
         const float4* __restrict__ prim_sp = S.prim_sp;
         const uint32_t* __restrict__ prim_idx = S.prim_idx;
-        // A leaf's spheres in list order, kLeafChunk loads in flight; a slot
-        // past the leaf's end reads the next leaf or the kPrimPad tail (in
-        // bounds) and is never tested.  prim_idx is read only for a sphere
-        // whose t passes the bound (closed: an equal t with a smaller index
-        // still gets in; a sphere met again in another leaf has the same t
-        // bits and the same index, and changes nothing).
-        auto leaf = [&](uint32_t off, uint32_t cnt) {
-            static_assert(kLeafChunk <= static_cast<int>(kPrimPad) + 1, "leaf loads may run past a leaf");
-            for (uint32_t j = 0; j < cnt; j += kLeafChunk) {
-                float4 sv[kLeafChunk];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) sv[s] = prim_sp[off + j + s];
-#pragma unroll
-                for (int s = 0; s < kLeafChunk; ++s) {
-                    if (j + s < cnt) {
-                        if (kStats) n_prims += 1;
-                        float th;
-                        if (sweep_isect(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, sv[s].x, sv[s].y, sv[s].z, sv[s].w, R,
-                                        tmin, tmax, kEntryOnly, th) &&
-                            th <= best_t) {
-                            const uint32_t ci = prim_idx[off + j + s];
-                            if (ci != self && (th < best_t || ci < best)) {
-                                best_t = th;
-                                best = ci;
-                            }
-                        }
-                    }
+        // prim_idx is read only for a sphere whose t passes the bound (closed:
+        // an equal t with a smaller index still gets in; a sphere met again in
+        // another leaf has the same t bits and the same index, and changes
+        // nothing)
+        auto test = [&](const float4& s, uint32_t slot) {
+            float th;
+            if (sweep_isect(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, s.x, s.y, s.z, s.w, R, tmin, tmax, kEntryOnly, th) &&
+                th <= best_t) {
+                const uint32_t ci = prim_idx[slot];
+                if (ci != self && (th < best_t || ci < best)) {
+                    best_t = th;
+                    best = ci;
                 }
             }
         };
+        auto leaf = [&](uint32_t off, uint32_t cnt) { leaf_spheres<kStats>(prim_sp, off, cnt, n_prims, test); };
         // (tmin < tmax: no t lies in any other window, a NaN end included)
         if (sweep_cast_ok(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, R) && tmin < tmax) {
             const SweepGuide sg = sweep_guide(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, R, S.rmin, S.scale,
@@ -122,63 +127,8 @@ __global__ void __launch_bounds__(kBlockThreads) sweep_kernel(FrameArgs a, Sweep
             // negative direction
             const uint32_t near = (sg.inv[0] < 0.0f ? 1u : 0u) | (sg.inv[1] < 0.0f ? 2u : 0u) |
                                   (sg.inv[2] < 0.0f ? 4u : 0u);
-            const bool in_root = sweep_meets(sweep_slab(sg, 0, 0.0f, S.G), sweep_slab(sg, 1, 0.0f, S.G),
-                                             sweep_slab(sg, 2, 0.0f, S.G), tmin, best_t);
-            if (in_root) {
-                if (kStats) n_nodes += 1;  // the root record
-                if (S.root_is_leaf) {
-                    if (S.root.y) leaf(S.root.x, S.root.y);  // an empty scene's root holds 0
-                } else {
-                    // the node the lane iterates: its record, depth, corner and
-                    // size, and the children still to visit in visiting order
-                    // (a mask that only loses bits)
-                    uint2 node = S.root;
-                    uint32_t depth = 0, l0 = 0, l1 = 0, l2 = 0, size = 1u << S.max_depth;
-                    float bound = best_t;  // the bound `rem` was last tested against
-                    uint32_t rem = sweep_children(sg, tmin, bound, l0, l1, l2, size >> 1, near) &
-                                   in_order(node.y & 0xFFu, near);
-                    for (;;) {
-                        if (rem == 0u) {
-                            if (depth == 0u) break;
-                            depth -= 1;
-                            size <<= 1;
-                            l0 &= ~(size - 1u);
-                            l1 &= ~(size - 1u);
-                            l2 &= ~(size - 1u);
-                            node = stk[depth * kBlockThreads];
-                            // the bound may have shrunk since this node was
-                            // left: it prunes the siblings queued then
-                            bound = best_t;
-                            rem = (node.y >> 16) & sweep_children(sg, tmin, bound, l0, l1, l2, size >> 1, near);
-                            continue;
-                        }
-                        const uint32_t c = static_cast<uint32_t>(__builtin_ctz(rem)) ^ near;
-                        rem &= rem - 1u;
-                        const uint32_t valid = node.y & 0xFFu;
-                        const uint2 rec = S.nodes[node.x + __builtin_popcount(valid & ((1u << c) - 1u))];
-                        if (kStats) n_nodes += 1;
-                        if ((node.y >> 8) & (1u << c)) {
-                            leaf(rec.x, rec.y);
-                            if (best_t < bound) {
-                                bound = best_t;
-                                rem &= sweep_children(sg, tmin, bound, l0, l1, l2, size >> 1, near);
-                            }
-                        } else if (depth < q.levels) {  // (always: the stack holds every internal depth)
-                            stk[depth * kBlockThreads] = make_uint2(node.x, (node.y & 0xFFFFu) | (rem << 16));
-                            const uint32_t half = size >> 1;
-                            l0 += (c & 1u) ? half : 0u;
-                            l1 += (c & 2u) ? half : 0u;
-                            l2 += (c & 4u) ? half : 0u;
-                            size = half;
-                            depth += 1;
-                            node = rec;
-                            bound = best_t;
-                            rem = sweep_children(sg, tmin, bound, l0, l1, l2, size >> 1, near) &
-                                  in_order(node.y & 0xFFu, near);
-                        }
-                    }
-                }
-            }
+            SegmentGuide guide = {sg, tmin, near, S.G, best_t, best_t};
+            descend<kStats>(S, stk, q.levels, guide, leaf, n_nodes);
         }
         q.hits[i] = make_uint2(__float_as_uint(best_t), best);
     }
@@ -208,10 +158,7 @@ hipError_t launch_sweep(const FrameArgs& a, const void* rays, const void* radii,
     q.n = n;
     q.radius = radius;
     q.skip_self = skip_self ? 1u : 0u;
-    // one level per depth that can hold an internal node (SceneArgs::
-    // stack_depth, as rt_closest.hip: this descent does not enter through the
-    // cell table either)
-    q.levels = a.sc.stack_depth ? a.sc.stack_depth : 1u;
+    q.levels = descent_levels(a.sc);
     q.slack_m = slack_m;
     q.counters = counters;
     const dim3 grid = query_grid(n), block(kBlockThreads);

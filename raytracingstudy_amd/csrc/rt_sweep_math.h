@@ -6,14 +6,7 @@
 // division).  rt_sweep.hip runs it per cast on the device, and
 // tests/native/sweep_math_dump.cpp prints it for tests/test_sweep_cpu.py.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define RT_SWP_HD __host__ __device__
-#else
-#define RT_SWP_HD
-#endif
+#include "rt_guide_math.h"
 
 namespace rtamd {
 
@@ -23,20 +16,19 @@ namespace rtamd {
 // 2^-18 in f32, in that order (a direction normalised in f32 is within
 // 4 * 2^-24).  R is in world units, so t has to be: the test below is a sphere
 // test for a unit direction only.  Any other cast misses.
-constexpr float kSweepUnitTol = 1.0f / 262144.0f;  // 2^-18
-RT_SWP_HD inline bool sweep_cast_ok(float ox, float oy, float oz, float dx, float dy, float dz, float R) {
-    const float big = 3.402823466e+38f;  // FLT_MAX: !(|x| <= big) <=> x is NaN or infinite
-    const bool finite = fabsf(ox) <= big && fabsf(oy) <= big && fabsf(oz) <= big && fabsf(dx) <= big &&
-                        fabsf(dy) <= big && fabsf(dz) <= big;
+constexpr float kGuideUnitTol = 1.0f / 262144.0f;  // 2^-18
+RT_GUIDE_HD inline bool sweep_cast_ok(float ox, float oy, float oz, float dx, float dy, float dz, float R) {
+    const bool finite = finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) &&
+                        finite_f32(dy) && finite_f32(dz);
     const float n2 = (dx * dx + dy * dy) + dz * dz;
-    return finite && R >= 0.0f && R <= big && fabsf(n2 - 1.0f) <= kSweepUnitTol;
+    return finite && R >= 0.0f && R <= kF32Max && fabsf(n2 - 1.0f) <= kGuideUnitTol;
 }
 
 // The frames' ray-sphere test (rt_walk.h isect, oracle.c:isect: the same fmaf
 // chain, the same window and the same fall-through to the far root) against
 // the sphere (c, s), s = r + R one f32 add.  entry_only: the near root alone
 // counts (RT_SWEEP_ENTRY_ONLY).
-RT_SWP_HD inline bool sweep_isect(float ox, float oy, float oz, float dx, float dy, float dz, float cx,
+RT_GUIDE_HD inline bool sweep_isect(float ox, float oy, float oz, float dx, float dy, float dz, float cx,
                                   float cy, float cz, float r, float R, float tmin, float tmax,
                                   bool entry_only, float& tout) {
     const float s = r + R;
@@ -100,21 +92,14 @@ constexpr double kSweepSlackM = 256.0;
 static_assert(kSweepSlackR >= kSweepNeedR + 6.0 && kSweepSlackO >= kSweepNeedO + 6.0 &&
                   kSweepSlackM >= kSweepNeedM + 6.0,
               "the grown cell covers the test's rounding, the slab roots' and its own");
-constexpr double kSweepU = 1.0 / 16777216.0;  // 2^-24
 
 // The scene's part of the slack: kSweepSlackM u M for the effective root box.
 inline float sweep_slack_m(const float rmin[3], const float rmax[3]) {
-    double m2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double a = fabs(static_cast<double>(rmin[i])), b = fabs(static_cast<double>(rmax[i]));
-        const double c = a > b ? a : b;
-        m2 += c * c;
-    }
-    return static_cast<float>(kSweepSlackM * kSweepU * sqrt(m2));
+    return static_cast<float>(kSweepSlackM * kGuideU * root_corner_far(rmin, rmax));
 }
 // The cast's part: kSweepSlackO u (|ox| + |oy| + |oz|), a bound of |o|.
-RT_SWP_HD inline float sweep_slack_o(float ox, float oy, float oz) {
-    return static_cast<float>(kSweepSlackO * kSweepU) * ((fabsf(ox) + fabsf(oy)) + fabsf(oz));
+RT_GUIDE_HD inline float sweep_slack_o(float ox, float oy, float oz) {
+    return static_cast<float>(kSweepSlackO * kGuideU) * ((fabsf(ox) + fabsf(oy)) + fabsf(oz));
 }
 
 // A cast in the walk's grid coordinates (SceneArgs::rmin, scale), made once:
@@ -124,9 +109,9 @@ RT_SWP_HD inline float sweep_slack_o(float ox, float oy, float oz) {
 struct SweepGuide {
     float og[3], inv[3], g[3];
 };
-RT_SWP_HD inline SweepGuide sweep_guide(float ox, float oy, float oz, float dx, float dy, float dz, float R,
+RT_GUIDE_HD inline SweepGuide sweep_guide(float ox, float oy, float oz, float dx, float dy, float dz, float R,
                                         const float rmin[3], const float scale[3], float slack) {
-    const float rel = static_cast<float>(1.0 + kSweepSlackR * kSweepU);
+    const float rel = static_cast<float>(1.0 + kSweepSlackR * kGuideU);
     const float grow = R * rel + slack;
     const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
     SweepGuide s;
@@ -146,7 +131,7 @@ RT_SWP_HD inline SweepGuide sweep_guide(float ox, float oy, float oz, float dx, 
 struct SweepSlab {
     float enter, exit;
 };
-RT_SWP_HD inline SweepSlab sweep_slab(const SweepGuide& s, int i, float k0, float k1) {
+RT_GUIDE_HD inline SweepSlab sweep_slab(const SweepGuide& s, int i, float k0, float k1) {
     const float a = ((k0 - s.g[i]) - s.og[i]) * s.inv[i];
     const float b = ((k1 + s.g[i]) - s.og[i]) * s.inv[i];
     const bool neg = s.inv[i] < 0.0f;  // (the reciprocal's sign: -0 counts as negative)
@@ -159,7 +144,7 @@ RT_SWP_HD inline SweepSlab sweep_slab(const SweepGuide& s, int i, float k0, floa
 // Whether the segment tmin < t <= bound may have its centre in the grown cell
 // whose three slabs these are: every prune written so that a NaN comparison
 // visits (fmaxf / fminf drop a NaN operand: that axis does not prune).
-RT_SWP_HD inline bool sweep_meets(const SweepSlab& x, const SweepSlab& y, const SweepSlab& z, float tmin,
+RT_GUIDE_HD inline bool sweep_meets(const SweepSlab& x, const SweepSlab& y, const SweepSlab& z, float tmin,
                                   float bound) {
     const float enter = fmaxf(fmaxf(x.enter, y.enter), z.enter);
     const float exit = fminf(fminf(x.exit, y.exit), z.exit);
