@@ -128,6 +128,10 @@ enum {
     /* A/B: no screen-space bins, every primary ray walks the octree (DESIGN.md
      * 5.1 round 10).  Images and counters are the same either way. */
     RT_FLAG_NO_BINS = 1u << 13,
+    /* A/B: no pixel pairs: a binned 33..64-spp frame shades one pixel a wave
+     * pass, as every other frame does.  Images and
+     * counters are the same either way. */
+    RT_FLAG_NO_PAIRS = 1u << 14,
     /* bits 16..19: scene-kernel variant for A/B runs (0 = default: 13, the
      * per-wave queue, for spp >= 8, else 7; others in DESIGN.md 5.1); images
      * and counters are identical across variants (packets: images only) */
@@ -294,6 +298,11 @@ typedef struct rt_bin_info {
                                  so 0 for frames queued before it                            */
 } rt_bin_info;
 int rt_get_bin_info(rt_renderer* r, rt_bin_info* info);
+/* The switches of the scene-kernel instance that the handle's last scene frame
+ * launched (tiles 1, stats 2, progressive 4, wave queue 8,
+ * sorted rounds 16, occluder lists 32, bins 64, pixel pairs 128); 0 before the
+ * first scene frame.  Does not wait. */
+uint32_t rt_last_instance(const rt_renderer* r);
 /* Copy the last frame's bins to host memory (sizes from rt_get_bin_info;
  * RT_E_STATE unless that frame built lists): headers_out 2*bins words, bin
  * b = by * ceil(W/8) + bx: {first entry, count}, a count of 0xFFFFFFFF: the

@@ -40,6 +40,7 @@ RT_FLAG_TEST_HOOKS = 1 << 10   # test-only: honour the RT_TEST_* environment var
 RT_FLAG_TEST_POISON = 1 << 11  # test-only: sentinel-fill every frame's outputs first
 RT_FLAG_NO_OCCLUDERS = 1 << 12  # A/B: every shadow ray walks the octree (no occluder lists)
 RT_FLAG_NO_BINS = 1 << 13  # A/B: every primary ray walks the octree (no screen-space bins)
+RT_FLAG_NO_PAIRS = 1 << 14  # A/B: binned 33..64-spp frames shade one pixel a wave pass
 RT_FLAG_VARIANT_SHIFT = 16
 RT_FLAG_OPT_SHIFT = 20
 RT_FLAG_CELL_TABLE_SHIFT = 28
@@ -249,6 +250,7 @@ SIGNATURES = {
     "rt_export_octree": (_int, [_P, _P, _P, _P]),
     "rt_export_occluders": (_int, [_P, _P, _P, _P, _P]),
     "rt_get_bin_info": (_int, [_P, ctypes.POINTER(RtBinInfo)]),
+    "rt_last_instance": (_u32, [_P]),
     "rt_export_bins": (_int, [_P, _P, _P, _P]),
     "rt_export_bin_tiles": (_int, [_P, _P, _P, _P, _P]),
     "rt_save_spheres": (_int, [ctypes.c_char_p, _P, _P, _u32]),

@@ -463,6 +463,8 @@ void* rt_framebuffer(rt_renderer* r) { return r ? r->fb.p : nullptr; }
 
 void* rt_stream(rt_renderer* r) { return r ? static_cast<void*>(own_stream(r)) : nullptr; }
 
+uint32_t rt_last_instance(const rt_renderer* r) { return r ? r->last_instance : 0u; }
+
 const char* rt_last_error(const rt_renderer* r) {
     if (r) return r->err.c_str();
     return g_last_error.c_str();

@@ -40,7 +40,7 @@ void fill_frame_args(rt_renderer* r, FrameArgs& a) {
         a.inv_spp = 1.0f / static_cast<float>((r->frames_accum + 1) * a.spp);
     }
     a.counters = r->counters.p;
-    a.sc.opt = (r->cfg.flags >> RT_FLAG_OPT_SHIFT) & 0xFFu;
+    a.sc.opt = ((r->cfg.flags >> RT_FLAG_OPT_SHIFT) & 0xFFu) | ((r->cfg.flags & RT_FLAG_NO_PAIRS) ? kOptNoPairs : 0u);
     a.wq_claim_delay = r->test_claim_delay;
     a.qerr = r->qerr_dev;
     if (++r->frame_seq == 0) r->frame_seq = 1;
@@ -374,7 +374,7 @@ inline int block_stats_end(rt_renderer*, const FrameArgs&, hipStream_t) { return
 int launch_frame(rt_renderer* r, FrameArgs& a, const FramePlan* plan, hipStream_t st) {
     int ost;
     if ((ost = timeline_begin(r, a, st)) || (ost = block_stats_begin(r, a, st))) return ost;
-    hipError_t e = plan ? launch_scene(a, *plan, st) : launch_compat(a, st);
+    hipError_t e = plan ? launch_scene(a, *plan, st, &r->last_instance) : launch_compat(a, st);
     counters_after_launch(r, a, e == hipSuccess);
     if (e != hipSuccess) return hip_fail(r, e, "kernel launch");
     if ((ost = block_stats_end(r, a, st)) || (ost = mark_queued(r, st))) return ost;

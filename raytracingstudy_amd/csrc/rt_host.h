@@ -34,7 +34,8 @@ namespace rtamd {
 
 // the kernels' launchers
 // rt_kernels.hip: a scene frame as do_render planned it (plan_scene_frame, rt_sched.h)
-hipError_t launch_scene(const FrameArgs& a, const FramePlan& plan, hipStream_t st);
+// (instance: the launched instance's Frame<> switches, rt_last_instance)
+hipError_t launch_scene(const FrameArgs& a, const FramePlan& plan, hipStream_t st, uint32_t* instance);
 bool variant_available(uint32_t v);
 // rt_compat.hip: the reference's frame restated; packed tiles scattered into the frame
 hipError_t launch_compat(const FrameArgs& a, hipStream_t st);
@@ -363,6 +364,7 @@ struct RendererState {
     // test only: RT_TEST_CLAIM_DELAY at rt_create with RT_FLAG_TEST_HOOKS
     // (FrameArgs::wq_claim_delay)
     uint32_t test_claim_delay = 0;
+    uint32_t last_instance = 0;  // Frame<> switches of the last scene launch (rt_last_instance)
     // test only, read at rt_create with RT_FLAG_TEST_HOOKS: the A/B switches
     // RT_SORT=0 (no sorted rounds), RT_LDS_STAGE=0 (no LDS leaf staging),
     // RT_LEAF_PACK=1 (line-packed leaf lists) and RT_SB_ORDER=1 (superblocks

@@ -286,6 +286,16 @@ __device__ __forceinline__ void scene_body(FrameArgs a) {
 #ifdef RT_TIMELINE
                 const unsigned long long tu0 = wall_clock64();
 #endif
+                if constexpr (C::pair) {
+                    // this pixel and the next of its ticket in one pass (pair_starts,
+                    // rt_sched.h); a pair that cannot be (shade_pixel_pair) is two
+                    // tiles of the one-pixel path below, the only call of it
+                    if (pair_starts(cur, w0, chunk) &&
+                        shade_pixel_pair<C>(ox, oy, n_primary, n_shadow, binc)) {
+                        ++cur;
+                        continue;
+                    }
+                }
                 if (kSort)
                     shade_pixel_sorted<C>(a, wl, stk, ox, oy, obase, n_primary, n_shadow, n_nodes,
                                           n_prims, bs);
@@ -476,11 +486,14 @@ static void launch_instance(FrameArgs a, const FramePlan& p, hipStream_t st) {
 // SceneInstance -> compiled instance: the 26 that exist, each for the frame
 // (kT = 0) and for a packed tile list (kT = kFTiles).  Written out, because a
 // generic flag-by-flag dispatch would instantiate combinations no frame runs.
+// (And the pair instance, which only frames run.)
 template <uint32_t kT>
 static bool launch_flags(uint32_t flags, const FrameArgs& a, const FramePlan& p, hipStream_t st) {
     switch (flags) {
 #define RT_INSTANCE(f) \
     case (f): launch_instance<Frame<(f) | kT>>(a, p, st); return true;
+#define RT_INSTANCE_FRAME(f) \
+    case (f): if constexpr (kT == 0u) { launch_instance<Frame<(f)>>(a, p, st); return true; } else return false;
 #define RT_INSTANCE_OCC(f) RT_INSTANCE(f) RT_INSTANCE((f) | kFOcc)
 #define RT_INSTANCE_OCC_BIN(f) RT_INSTANCE_OCC(f) RT_INSTANCE_OCC((f) | kFBin)
         // stats frames: they walk and count (7 waves per SIMD: the counters
@@ -503,6 +516,11 @@ static bool launch_flags(uint32_t flags, const FrameArgs& a, const FramePlan& p,
         RT_INSTANCE_OCC_BIN(kFWaveQ | kFProg)
         RT_INSTANCE_OCC_BIN(kFWaveQ | kFSorted)
         RT_INSTANCE_OCC_BIN(kFWaveQ | kFSorted | kFProg)
+        // a binned plain frame of one-pixel wave tiles in one round (33 .. 64
+        // spp): two pixels a wave pass (round 26)
+        // (the frame only: launch_scene)
+        RT_INSTANCE_FRAME(kFWaveQ | kFOcc | kFBin | kFPair)
+#undef RT_INSTANCE_FRAME
 #undef RT_INSTANCE_OCC_BIN
 #undef RT_INSTANCE_OCC
 #undef RT_INSTANCE
@@ -517,14 +535,18 @@ bool variant_available(uint32_t v) {
 
 // p: the frame's plan (do_render made it; the frame's occluder lists and
 // bins, which the steps since filled in, finish its instance)
-hipError_t launch_scene(const FrameArgs& a_in, const FramePlan& p, hipStream_t st) {
+hipError_t launch_scene(const FrameArgs& a_in, const FramePlan& p, hipStream_t st, uint32_t* instance) {
     FrameArgs a = a_in;
     // (bins: set only for a frame whose instance reads them, bins_gate)
-    const SceneInstance inst =
+    SceneInstance inst =
         p.inst.with(a.sc.prim_occ && a.sc.occ_sp && a.shadows, a.bin_hdr && a.bin_ent && a.bin_info);
+    // packed tiles keep the one-pixel path: with pairs the tile instance needs 64
+    // bytes of scratch, and a 1/8 C3 share measured +1.2% (round 26)
+    if (a.tiles) inst.pair = false;
     a.spw = p.spw, a.g = p.g, a.ppw = p.ppw, a.rounds = p.rounds;
     a.tw = p.grid.tw, a.th = p.grid.th;
     a.wq_chunk = p.ticket;  // (the wave queue's launch may cap it)
+    *instance = inst.flags() | (a.tiles ? kFTiles : 0u);
     // (an instance outside the table: a bug in pick_scene_instance, a failed frame)
     const bool known = inst.valid && (a.tiles ? launch_flags<kFTiles>(inst.flags(), a, p, st)
                                               : launch_flags<0u>(inst.flags(), a, p, st));

@@ -29,6 +29,9 @@ constexpr uint32_t kOptChunkShift = 4;     // bits 4..6: wave-queue tiles per ti
                                            // 5..7 are refused (a ticket must not span half
                                            // a slot: the two-level queue's claim rule)
 constexpr uint32_t kOptChunkMax = 4;
+constexpr uint32_t kOptNoPairs = 1u << 8;  // bit 8 (RT_FLAG_NO_PAIRS: the eight rt_config bits are
+                                           // taken): no pixel pairs (kFPair), every wave tile
+                                           // takes the one-pixel path
 
 // scene kernel variants (rt_config.flags bits 16..19, RT_FLAG_VARIANT_SHIFT);
 // 0 picks 13 for spp >= 8, else 4 (default_variant).  Numbers of the variants
@@ -150,13 +153,14 @@ enum FrameFlag : uint32_t {
     kFSorted = 1u << 4,  // quadrant-sorted rounds, one pixel per wave
     kFOcc = 1u << 5,     // shadow rays answered from the occluder lists
     kFBin = 1u << 6,     // primary rays answered from the frame's screen-space bins
+    kFPair = 1u << 7,    // one-pixel wave tiles shaded two to a wave pass (shade_pixel_pair)
 };
 
 template <uint32_t kF>
 struct Frame {
     static constexpr bool tiles = kF & kFTiles, stats = kF & kFStats, prog = kF & kFProg,
                           waveq = kF & kFWaveQ, sorted = kF & kFSorted, occ = kF & kFOcc,
-                          bin = kF & kFBin;
+                          bin = kF & kFBin, pair = kF & kFPair;
     // waves per SIMD asked of the register allocator: plain wave-queue frames
     // are the 8-wave build (scene_kernel_w8), stats frames keep 7
     static constexpr int min_waves = waveq ? (stats ? 7 : 8) : 1;
@@ -166,14 +170,20 @@ struct Frame {
     static_assert(!sorted || waveq, "sorted rounds: a wave-queue frame");
     static_assert(!occ || !stats, "stats frames walk: their counters are the oracle's");
     static_assert(!bin || (!stats && waveq), "bins: plain frames of the wave queue");
+    static_assert(!pair || (bin && occ && !sorted && !prog && !tiles),
+                  "pairs: binned plain frames with occluder lists, not packed tiles");
 };
 
 struct SceneInstance {
     bool valid;  // false: a variant this build does not have
     bool waveq, stats, prog, sorted, occ, bin;
+    // pair_shape: the frame's wave tile is one pixel in one round and pairs are
+    // not switched off (plan_scene_frame); pair: such a frame of an instance
+    // that has the pair path (with())
+    bool pair_shape, pair;
     RT_HD uint32_t flags() const {  // without kFTiles: the launcher's
         return (stats ? kFStats : 0u) | (prog ? kFProg : 0u) | (waveq ? kFWaveQ : 0u) |
-               (sorted ? kFSorted : 0u) | (occ ? kFOcc : 0u) | (bin ? kFBin : 0u);
+               (sorted ? kFSorted : 0u) | (occ ? kFOcc : 0u) | (bin ? kFBin : 0u) | (pair ? kFPair : 0u);
     }
     RT_HD uint32_t min_waves() const { return waveq ? (stats ? 7u : 8u) : 1u; }
     RT_HD bool w8() const { return waveq && !stats; }  // scene_kernel_w8: the instances that read bins
@@ -182,6 +192,7 @@ struct SceneInstance {
         SceneInstance s = *this;
         s.occ = !stats && have_occ;
         s.bin = !stats && waveq && have_bins;
+        s.pair = pair_shape && s.bin && s.occ && !sorted && !prog;
         return s;
     }
 };
@@ -197,7 +208,7 @@ RT_HD inline SceneInstance pick_scene_instance(uint32_t variant, uint32_t spp, b
                                                bool count_work, bool sort_on, bool have_occ,
                                                bool have_bins, uint32_t tab_k, uint32_t stack_depth) {
     if (!variant) variant = default_variant(spp);
-    SceneInstance s = {true, false, count_work, progressive, false, false, false};
+    SceneInstance s = {true, false, count_work, progressive, false, false, false, false, false};
     const uint32_t rounds = (spp + 63u) / 64u;
     s.sorted = sort_on && spp >= 64u && rounds >= 2u && rounds <= kSortMaxRounds &&
                FrameLds(true, tab_k, stack_depth).bytes * 8u <= 160u * 1024u &&
@@ -241,6 +252,8 @@ RT_HD inline FramePlan plan_scene_frame(uint32_t variant, uint32_t spp, bool pro
     uint32_t tw, th;
     wave_tile_shape(spp, p.spw, p.g, p.ppw, tw, th);
     p.rounds = (spp + p.spw - 1) / p.spw;
+    // pixel pairs (kFPair): a wave tile is one pixel, shaded in one round (33 .. 64 spp)
+    p.inst.pair_shape = p.ppw == 1u && p.rounds == 1u && !(opt & kOptNoPairs);
     p.slot_shift = p.grid.slot_shift();
     p.slot_stride = p.grid.slot_stride();
     p.lds_bytes = FrameLds(p.inst.sorted, tab_k, stack_depth).bytes;
@@ -252,6 +265,16 @@ RT_HD inline FramePlan plan_scene_frame(uint32_t variant, uint32_t spp, bool pro
     p.ticket = ck ? 1u << (ck - 1u) : 4u / (p.rounds < 1u ? 1u : p.rounds > 4u ? 4u : p.rounds);
     p.ticket_forced = ck != 0u;
     return p;
+}
+
+// Pixel pairs (kFPair, rt_shade.h shade_pixel_pair): inside a ticket's wave
+// tiles [w0, w0 + chunk) of a slot, tile cur starts a pair with cur + 1 when it
+// is even and cur + 1 belongs to the ticket.  A slot's tiles are numbered row
+// by row in 8-wide blocks (scene_body), so the two are the pixels (x, y) and
+// (x + 1, y), x even, of one block row: one 8x8 bin.  A tile that starts no
+// pair and is not the second of one is shaded alone.
+RT_HD inline bool pair_starts(uint32_t cur, uint32_t w0, uint32_t chunk) {
+    return (cur & 1u) == 0u && cur + 1u < w0 + chunk;
 }
 
 // ---------------------------------------------------------------------------

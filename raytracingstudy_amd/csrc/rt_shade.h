@@ -264,4 +264,218 @@ __device__ __forceinline__ void shade_wave_tile(const FrameArgs& a, float4* acc,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Pixel pairs (Frame<kFPair>)
+//
+// A binned plain frame of 33 .. 64 spp gives a wave one pixel: everything
+// wave-uniform (the bin's header, the entries' scalar loads and loop control,
+// the kernel-argument reads, the butterfly's trips, the output address) is
+// paid once a pixel.  Here a lane carries sample s of pixel A = (x, y) AND of
+// pixel B = (x + 1, y), x even: the two lie in one bin, so the wave does that
+// work once for both.  Per pixel nothing changes: the same ray, the entries of
+// its own tile word in the list's order with its own near-bound break, the
+// same tie rule, the same shading operands and the butterfly's pairing.
+//
+// False: the pair was not shaded and nothing was written or counted (the
+// frame's flag, a bin over the cap, a hit sphere whose
+// shadow rays walk the octree): the caller shades A and B by the one-pixel
+// path, which holds the kernel's only copies of the walks.
+// ---------------------------------------------------------------------------
+
+typedef uint32_t pair_u32x4 __attribute__((ext_vector_type(4), aligned(8)));
+
+// one pixel's samples of a pair
+struct PairRay {
+    float d0, d1, d2;
+};
+
+__device__ __forceinline__ PairRay pair_ray(KernArgs* ka, uint32_t x, uint32_t y, uint32_t hp, uint32_t s) {
+    float u = static_cast<float>(x), v = static_cast<float>(y);
+    if (ka->jitter) {
+        u = u + u01(mix32(hp ^ (s << 1)));
+        v = v + u01(mix32(hp ^ ((s << 1) | 1u)));
+    }
+    CamArgs cam;
+    for (int i = 0; i < 9; ++i) cam.K[i] = ka->cam.K[i], cam.R[i] = ka->cam.R[i];
+    PairRay r;
+    get_ray(cam, u, v, r.d0, r.d1, r.d2);
+    return r;
+}
+
+// A hit's shading (sample_color_unified's, same operands in the same order):
+// Lambert term, whether a shadow ray is wanted and its origin.
+struct PairShade {
+    float lam, o0, o1, o2;
+    bool want;
+};
+__device__ __forceinline__ PairShade pair_shade(KernArgs* kb, float4 sp, float r0, float r1, float r2,
+                                                const PairRay& d, float t, bool hit) {
+    const float p0 = r0 + t * d.d0;
+    const float p1 = r1 + t * d.d1;
+    const float p2 = r2 + t * d.d2;
+    const float ir = 1.0f / sp.w;
+    const float n0 = (p0 - sp.x) * ir;
+    const float n1 = (p1 - sp.y) * ir;
+    const float n2 = (p2 - sp.z) * ir;
+    const float ndl = n0 * kb->L[0] + n1 * kb->L[1] + n2 * kb->L[2];
+    PairShade s;
+    s.lam = hit && ndl > 0.0f ? ndl : 0.0f;
+    s.want = hit && ndl > 0.0f && kb->shadows;
+    s.o0 = p0 + n0 * kShadowEps;
+    s.o1 = p1 + n1 * kShadowEps;
+    s.o2 = p2 + n2 * kShadowEps;
+    return s;
+}
+
+__device__ __forceinline__ PixelOut pair_color(float amb, bool hit, float lam, uint32_t al, const PairRay& d) {
+    PixelOut c{200.0f / 255.0f, sat(d.d1), sat(d.d2)};
+    if (hit) {
+        const float f = amb + (1.0f - amb) * lam;
+        c.r = static_cast<float>(al & 0xFFu) * (1.0f / 255.0f) * f;
+        c.g = static_cast<float>((al >> 8) & 0xFFu) * (1.0f / 255.0f) * f;
+        c.b = static_cast<float>((al >> 16) & 0xFFu) * (1.0f / 255.0f) * f;
+    }
+    return c;
+}
+
+// (ox, oy): pixel A, ox even; binc: bin_frame_consts.
+template <class C>
+__device__ __forceinline__ bool shade_pixel_pair(uint32_t ox, uint32_t oy, uint32_t& n_primary,
+                                                 uint32_t& n_shadow, uint32_t binc) {
+    static_assert(C::pair && !C::tiles, "a frame instance with the pair path");
+    KernArgs* ka = kernargs();
+    const uint32_t W = ka->W;
+    if (bin_consts_flag(binc)) return false;
+    // the bin's header and both tile words: adjacent, A's first (x even)
+    const uint32_t b = (oy >> kBinShift) * ka->bin_nbx + (ox >> kBinShift);
+    const bin_u32x2 h = *reinterpret_cast<__attribute__((address_space(4))) const bin_u32x2*>(
+        reinterpret_cast<uintptr_t>(ka->bin_hdr + b));
+    const size_t wi = (static_cast<size_t>(b) << (2u * kBinShift)) + bin_tile_index_log2(ox, oy, 0u, 0u);
+    const pair_u32x4 w = *reinterpret_cast<__attribute__((address_space(4))) const pair_u32x4*>(
+        reinterpret_cast<uintptr_t>(ka->bin_hdr + ka->bin_nb + wi));
+    if (h.y == kBinWalk) return false;
+    const bool b_on = ox + 1u < W;  // B off the image (an odd width): its lanes take no part
+    unsigned long long wa = h.y ? (static_cast<unsigned long long>(w.y) << 32) | w.x : 0ull;
+    unsigned long long wb = h.y && b_on ? (static_cast<unsigned long long>(w.w) << 32) | w.z : 0ull;
+
+    // (made here from the thread index each time: as a loop invariant of the
+    // queue loop the lane index was spilled to scratch and reloaded per pair)
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const uint32_t lane = tid & 63u;
+    const bool va = lane < ka->spw, vb = va && b_on;
+    const uint32_t pid = oy * W + ox;
+    const uint32_t seedmix = ka->seedmix;
+    const PairRay da = pair_ray(ka, ox, oy, mix32(seedmix ^ pid), lane);
+    const PairRay db = pair_ray(ka, ox + 1u, oy, mix32(seedmix ^ (pid + 1u)), lane);
+    const float r0 = ka->cam.o[0], r1 = ka->cam.o[1], r2 = ka->cam.o[2];
+
+    // the entries of wa | wb, lowest first; a pixel takes part in those of its
+    // own word until its near-bound break (bin_nearest's loop, per pixel)
+    BinBest ba{va ? INFINITY : -INFINITY, kNoHit, kNoHit};
+    BinBest bb{vb ? INFINITY : -INFINITY, kNoHit, kNoHit};
+    BinEntries* ent = reinterpret_cast<BinEntries*>(reinterpret_cast<uintptr_t>(ka->bin_ent)) + h.x;
+    while (wa | wb) {
+        const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(wa | wb));
+        const unsigned long long bit = 1ull << k;
+        const bin_u32x8 e = ent[k];
+        const bool in_a = (wa & bit) != 0ull, in_b = (wb & bit) != 0ull;
+        wa &= ~bit;
+        wb &= ~bit;
+        if (in_a && !bin_entry(e, r0, r1, r2, da.d0, da.d1, da.d2, ba)) wa = 0ull;
+        if (in_b && !bin_entry(e, r0, r1, r2, db.d0, db.d1, db.d2, bb)) wb = 0ull;
+    }
+    const uint32_t nw = bin_consts_wide(binc);
+    if (nw) {  // the wide list: every entry against both pixels, each to its own break
+        BinEntries* wide = reinterpret_cast<BinEntries*>(reinterpret_cast<uintptr_t>(ka->bin_wide));
+        bool on_a = true, on_b = b_on;
+        for (uint32_t k = 0; k < nw && (on_a || on_b); ++k) {
+            const bin_u32x8 e = wide[k];
+            if (on_a) on_a = bin_entry(e, r0, r1, r2, da.d0, da.d1, da.d2, ba);
+            if (on_b) on_b = bin_entry(e, r0, r1, r2, db.d0, db.d1, db.d2, bb);
+        }
+    }
+    const bool hit_a = ba.ref != kNoHit, hit_b = bb.ref != kNoHit;
+
+    // shading: one region for "A or B hit", the six records in front of one
+    // wait.  A pixel that missed reads the other's reference (a valid one) and
+    // keeps none of what it computes from it.
+    float lam_a = 0.0f, lam_b = 0.0f;
+    uint32_t al_a = 0, al_b = 0;
+    uint2 occ_a = make_uint2(0u, 0u), occ_b = make_uint2(0u, 0u);
+    PairShade sa{0.0f, 0.0f, 0.0f, 0.0f, false}, sb = sa;
+    if (hit_a || hit_b) {
+        KernArgs* kb = kernargs();
+        const uint32_t ia = hit_a ? ba.ref : bb.ref, ib = hit_b ? bb.ref : ba.ref;
+        const float4 sp_a = kb->sc.prim_sp[ia];
+        const float4 sp_b = kb->sc.prim_sp[ib];
+        al_a = kb->sc.prim_al[ia];
+        al_b = kb->sc.prim_al[ib];
+        occ_a = kb->sc.prim_occ[ia];
+        occ_b = kb->sc.prim_occ[ib];
+        sa = pair_shade(kb, sp_a, r0, r1, r2, da, ba.t, hit_a);
+        sb = pair_shade(kb, sp_b, r0, r1, r2, db, bb.t, hit_b);
+        lam_a = sa.lam, lam_b = sb.lam;
+    }
+    const bool want_a = sa.want, want_b = sb.want;
+    // a hit sphere without a list: its rays walk, by the one-pixel path (decided
+    // by the whole wave, outside the lanes' region)
+    if (__any((want_a && occ_a.y == kOccWalk) || (want_b && occ_b.y == kOccWalk))) return false;
+    if (want_a || want_b) {
+        // both pixels' occluder lists in one loop, each lane to its own list's
+        // end or first occluder (shadow_occluded's loop, per pixel); a lane
+        // with no candidate left reads occ_sp[0] and keeps nothing of it
+        KernArgs* kl = kernargs();
+        const float l0 = kl->L[0], l1 = kl->L[1], l2 = kl->L[2];
+        const float4* __restrict__ lst = kl->sc.occ_sp;
+        const uint32_t cnt_a = want_a ? occ_a.y : 0u, cnt_b = want_b ? occ_b.y : 0u;
+        bool oc_a = false, oc_b = false;
+        for (uint32_t k = 0;; ++k) {
+            const bool go_a = k < cnt_a && !oc_a, go_b = k < cnt_b && !oc_b;
+            if (!(go_a || go_b)) break;
+            const float4 ca = lst[go_a ? occ_a.x + k : 0u];
+            const float4 cb = lst[go_b ? occ_b.x + k : 0u];
+            float th;
+            const bool xa = isect(sa.o0, sa.o1, sa.o2, l0, l1, l2, ca, 0.0f, INFINITY, th);
+            const bool xb = isect(sb.o0, sb.o1, sb.o2, l0, l1, l2, cb, 0.0f, INFINITY, th);
+            oc_a = go_a ? xa : oc_a;
+            oc_b = go_b ? xb : oc_b;
+        }
+        if (oc_a) lam_a = 0.0f;
+        if (oc_b) lam_b = 0.0f;
+    }
+    n_primary += static_cast<uint32_t>(__popcll(__ballot(va)) + __popcll(__ballot(vb)));
+    n_shadow += static_cast<uint32_t>(__popcll(__ballot(want_a)) + __popcll(__ballot(want_b)));
+
+    // both pixels' sums in the butterfly's six trips (tree_sum's pairing for
+    // each); every lane ends with both sums, bit for bit the leader's
+    const float amb = kernargs()->ambient;
+    PixelOut ca = pair_color(amb, hit_a, lam_a, al_a, da);
+    PixelOut cb = pair_color(amb, hit_b, lam_b, al_b, db);
+    if (!va) ca = PixelOut{0.0f, 0.0f, 0.0f};
+    if (!vb) cb = PixelOut{0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (uint32_t m = 1; m < 64u; m <<= 1) {
+        const float ar = __shfl_xor(ca.r, static_cast<int>(m), 64), ag = __shfl_xor(ca.g, static_cast<int>(m), 64),
+                    ab = __shfl_xor(ca.b, static_cast<int>(m), 64), br = __shfl_xor(cb.r, static_cast<int>(m), 64),
+                    bg = __shfl_xor(cb.g, static_cast<int>(m), 64), bl = __shfl_xor(cb.b, static_cast<int>(m), 64);
+        ca.r += ar, ca.g += ag, ca.b += ab;
+        cb.r += br, cb.g += bg, cb.b += bl;
+    }
+    // lane 0 writes A and lane 1 writes B: adjacent words, one store
+    KernArgs* ko = kernargs();
+    if (lane < 2u) {
+        const bool second = lane != 0u;
+        const float isp = ko->inv_spp;
+        const PixelOut p{(second ? cb.r : ca.r) * isp, (second ? cb.g : ca.g) * isp, (second ? cb.b : ca.b) * isp};
+        const uint32_t rgba = pack_rgba8(p);
+        if (!second || b_on) {
+            const size_t o = (size_t)oy * ko->W + ox + lane;
+            ko->out8[o] = rgba;
+            if (ko->out32) ko->out32[o] = make_float4(p.r, p.g, p.b, 1.0f);
+        }
+    }
+    return true;
+}
+
 }  // namespace rtamd

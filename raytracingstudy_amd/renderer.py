@@ -141,7 +141,7 @@ class KernelRenderer:
                  variant: int = 0, opt_off: int = 0, host_build: bool = False,
                  progressive: bool = False, cell_table: Optional[int] = None,
                  compat_fma: bool = False, pad_fill: int = 0, occluders: bool = True,
-                 bins: bool = True,
+                 bins: bool = True, pairs: bool = True,
                  devices: Optional[Sequence[int]] = None, transport: str = "auto"):
         """devices: render every frame across these HIP devices of this process
         (rt_create_multi: tiles round-robin, slabs gathered to devices[0] over
@@ -174,6 +174,8 @@ class KernelRenderer:
             flags |= _lib.RT_FLAG_NO_OCCLUDERS
         if not bins:  # A/B: every primary ray walks the octree
             flags |= _lib.RT_FLAG_NO_BINS
+        if not pairs:  # A/B: one pixel a wave pass in every frame
+            flags |= _lib.RT_FLAG_NO_PAIRS
         # pad_fill (test-only): 0 zeros, 1 NaN, 2 covering spheres after the last leaf list
         if not 0 <= int(pad_fill) <= 2:
             raise ValueError("pad_fill must be 0, 1 or 2")
@@ -326,6 +328,11 @@ class KernelRenderer:
         info = _lib.RtBinInfo()
         check(self._lib.rt_get_bin_info(self._h, ctypes.byref(info)), self._h)
         return info.as_dict()
+
+    def last_instance(self) -> int:
+        """rt_last_instance: the Frame<> switches of the last scene frame's kernel
+        (bit 7, 128: pixel pairs)."""
+        return int(self._lib.rt_last_instance(self._h))
 
     def export_bins(self):
         """The last frame's bins as host arrays (rt_export_bins): (bins, 2)

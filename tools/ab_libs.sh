@@ -8,6 +8,8 @@
 # usage: bash tools/ab_libs.sh <log> <configs> <reps> <name>...
 #   TOOL=variants (default): tools/variants.py plain frames of <configs>
 #   TOOL=share:              tools/share_cost.py (1/8 C3 tile share + full frame)
+#   TOOL=bench:              bench.py --steps 200 --warmup 10 of <configs> (the headline's
+#                            ms_per_step; BENCH_ARGS: further arguments, e.g. "--shard 0/8")
 #   ENV="A=1 B=2":           extra environment for every run
 #   HOOKS=1:                 TOOL=variants makes its renderers with RT_FLAG_TEST_HOOKS
 #                            (_lib.test_flags), so the library reads its A/B switches
@@ -19,7 +21,7 @@ LOG=${1:?log}; CFGS=${2:?configs}; REPS=${3:?reps}; shift 3
 TOOL=${TOOL:-variants}
 export TMPDIR=/tmp
 mkdir -p "$(dirname "$LOG")"
-echo "# cmd: TOOL=$TOOL HOOKS=${HOOKS:-} ENV='${ENV:-}' bash tools/ab_libs.sh $LOG $CFGS $REPS $*" >> "$LOG"
+echo "# cmd: TOOL=$TOOL HOOKS=${HOOKS:-} ENV='${ENV:-}'${BENCH_ARGS:+ BENCH_ARGS='$BENCH_ARGS'} bash tools/ab_libs.sh $LOG $CFGS $REPS $*" >> "$LOG"
 for i in $(seq "$REPS"); do
   for L in "$@"; do
     case $TOOL in
@@ -29,6 +31,13 @@ for i in $(seq "$REPS"); do
       share)
         env ${ENV:-} RT_AMD_LIB=$PWD/abl/librt_$L.so timeout -k 10 120 python tools/share_cost.py \
             2>/dev/null | sed "s/^/$L /" >> "$LOG" ;;
+      bench)
+        for C in ${CFGS//,/ }; do
+          env ${ENV:-} RT_AMD_LIB=$PWD/abl/librt_$L.so timeout -k 10 200 python bench.py --gpus 1 --steps 200 \
+              --warmup 10 --config "$C" --cpu-baseline off --secondary= ${BENCH_ARGS:-} 2>/dev/null |
+              python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({"config": sys.argv[1], "ms_per_step": d["ms_per_step"], "kernel_ms": d["config"].get("kernel_ms")}))' "$C" |
+              sed "s/^/$L /" >> "$LOG"
+        done ;;
       *) echo "unknown TOOL=$TOOL" >&2; exit 2 ;;
     esac
   done

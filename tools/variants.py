@@ -37,7 +37,7 @@ def main():
     if args.test_hooks:
         rt._lib.test_flags = rt._lib.RT_FLAG_TEST_HOOKS
     # a variant spec is "V", "V:OPT", "V:OPT:T", "V:OPT:T:CAP" or "V:OPT:T:CAP:OCC"
-    # (OPT = rt_config opt bits, A/B toggles; T = cell-table depth: 0 off, 1..7,
+    # (OPT = rt_config opt bits, A/B toggles, and 256: no pixel pairs; T = cell-table depth: 0 off, 1..7,
     # absent = chosen from the tree; CAP = octree leaf capacity, absent = the
     # config's; OCC = 0: no occluder lists, every shadow ray walks)
     variants = args.variants.split(",")
@@ -55,8 +55,8 @@ def main():
             tt, _, rest = rest.partition(":")
             cc, _, occ = rest.partition(":")
             r = rt.KernelRenderer(cfg.width, cfg.height, mode="scene", spp=spp, variant=int(vv),
-                                  opt_off=int(oo or 0), cell_table=int(tt) if tt else None,
-                                  occluders=occ != "0")
+                                  opt_off=int(oo or 0) & 0xFF, cell_table=int(tt) if tt else None,
+                                  occluders=occ != "0", pairs=not int(oo or 0) & 0x100)
             r.resize(cfg.width, cfg.height)
             r.setPosition(scene_pose())
             info = r.set_scene(sp, al, max_depth=cfg.max_depth,
