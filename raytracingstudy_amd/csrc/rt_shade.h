@@ -429,20 +429,26 @@ __device__ __forceinline__ bool shade_pixel_pair(uint32_t ox, uint32_t oy, uint3
         const float l0 = kl->L[0], l1 = kl->L[1], l2 = kl->L[2];
         const float4* __restrict__ lst = kl->sc.occ_sp;
         const uint32_t cnt_a = want_a ? occ_a.y : 0u, cnt_b = want_b ? occ_b.y : 0u;
-        bool oc_a = false, oc_b = false;
+        // The state carried round the loop is plain data: a list end per pixel,
+        // which its first occluder sets to 0 (so "occluded" is end != cnt), and
+        // the wave leaves together once no lane has a candidate left.  (Round
+        // 27: with each lane leaving on its own and "occluded" carried as
+        // bools, the loop's body block held 26 scalar instructions of
+        // exec-mask bookkeeping against 7, and 6 more VALU: C3 -2.8%.)
+        uint32_t end_a = cnt_a, end_b = cnt_b;
         for (uint32_t k = 0;; ++k) {
-            const bool go_a = k < cnt_a && !oc_a, go_b = k < cnt_b && !oc_b;
-            if (!(go_a || go_b)) break;
+            const bool go_a = k < end_a, go_b = k < end_b;
+            if (!__any(go_a | go_b)) break;
             const float4 ca = lst[go_a ? occ_a.x + k : 0u];
             const float4 cb = lst[go_b ? occ_b.x + k : 0u];
             float th;
             const bool xa = isect(sa.o0, sa.o1, sa.o2, l0, l1, l2, ca, 0.0f, INFINITY, th);
             const bool xb = isect(sb.o0, sb.o1, sb.o2, l0, l1, l2, cb, 0.0f, INFINITY, th);
-            oc_a = go_a ? xa : oc_a;
-            oc_b = go_b ? xb : oc_b;
+            end_a = (go_a & xa) ? 0u : end_a;
+            end_b = (go_b & xb) ? 0u : end_b;
         }
-        if (oc_a) lam_a = 0.0f;
-        if (oc_b) lam_b = 0.0f;
+        if (end_a != cnt_a) lam_a = 0.0f;
+        if (end_b != cnt_b) lam_b = 0.0f;
     }
     n_primary += static_cast<uint32_t>(__popcll(__ballot(va)) + __popcll(__ballot(vb)));
     n_shadow += static_cast<uint32_t>(__popcll(__ballot(want_a)) + __popcll(__ballot(want_b)));
