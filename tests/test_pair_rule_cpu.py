@@ -28,13 +28,15 @@ def dump(tmp_path_factory):
 
 # odd and even widths, edge blocks (no multiple of 8), a full block, one column
 GRIDS = [(8, 8), (7, 5), (6, 8), (1, 3), (2, 1), (13, 9), (14, 12), (64, 64), (63, 45), (62, 44), (57, 64)]
+# the pair fuzz's narrow frames (tests/pair_fuzz.py SMALL_W: each side of one bin), heights from 1
+GRIDS += [(1, 1), (1, 9), (2, 7), (3, 1), (3, 8), (7, 9), (8, 1), (9, 1), (9, 8), (9, 17), (15, 3), (17, 9)]
 
 
 # (a block slot, ks = 6, holds 8x8 wave tiles; a superblock slot 64x64)
 SLOTS = [(gw, gh, ks) for gw, gh in GRIDS for ks in (6, 12) if ks == 12 or (gw <= 8 and gh <= 8)]
 
 
-@pytest.mark.parametrize("chunk", [1, 2, 4])
+@pytest.mark.parametrize("chunk", [1, 2, 4, 8])       # (8: the option field's largest, a block's row)
 @pytest.mark.parametrize("gw,gh,ks", SLOTS)
 def test_pairs_cover_a_slot_once(dump, gw, gh, chunk, ks):
     seen, pairs, singles = {}, 0, 0
@@ -68,7 +70,8 @@ def test_the_plan_chooses_the_pair_instance(dump):
     for spp in (33, 48, 64):
         assert flags(spp) == WAVEQ | OCC | BIN_ | PAIR
         assert flags(spp, opt=NO_PAIRS) == WAVEQ | OCC | BIN_
-        assert flags(spp, opt=2 << 4) == WAVEQ | OCC | BIN_ | PAIR      # (a ticket size changes nothing)
+        for k in (1, 2, 3, 4):                                          # (a ticket size changes nothing)
+            assert flags(spp, opt=k << 4) == WAVEQ | OCC | BIN_ | PAIR
         assert flags(spp, occ=0) == WAVEQ | BIN_
         assert flags(spp, bins=0) == WAVEQ | OCC
         assert flags(spp, stats=1) & (PAIR | BIN_ | OCC) == 0
