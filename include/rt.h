@@ -38,7 +38,7 @@
  *     mouse input selects nothing)
  *   (none: as above; one hit was the most a ray           rt_trace_rays_multi / rt_pick_multi
  *     could report)
- *   (none: one colour per pixel,                          rt_render_gbuffer
+ *   (none: one colour per pixel,                          rt_render_gbuffer, rt_render_ao
  *     src/renderer.cu:57-82)
  *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
  *     the octree which spheres touch a ball)
@@ -661,6 +661,40 @@ typedef struct rt_gbuffer {
  * accumulation, counters, the framebuffer, the next frame's image).  A
  * multi-device handle answers from devices[0] with the whole frame. */
 int rt_render_gbuffer(rt_renderer* r, const rt_gbuffer* out, void* stream, rt_stats* stats);
+
+/* ---- ambient-occlusion layer ---------------------------------------------- */
+/* The depth cue of a sphere cloud: from every pixel's first hit (the G-buffer's:
+ * rt_pick(x, y)'s ray and hit; a camera inside a sphere reports the far root),
+ * `rays` short any-hit rays, cosine-weighted about the hit's shading normal, and
+ * the share of them that reach `radius` unoccluded.  A viewer multiplies the
+ * layer into its frame.  The reference has no counterpart.
+ * Ray i of pixel (x, y), exactly in f32: origin p + n * 1e-5
+ * with p = o + t*d and n = (p - c) * (1.0f / r), the frames' shadow-ray origin;
+ * direction (n + s) / |n + s|, s a point of the unit sphere hashed from (the
+ * renderer's seed, salt, y*W + x, i), or n where that degenerates; tmin = 0,
+ * tmax = radius; rt_trace_rays' RT_QUERY_ANY test.  A miss pixel casts nothing.
+ * Every pixel of each given buffer is written (row-major, pixel y*W + x). */
+typedef struct rt_ao_params {
+    uint32_t rays;    /* AO rays per hit pixel: 1, 2, 4, 8, 16, 32 or 64 */
+    float    radius;  /* each AO ray's tmax in world units: > 0, +inf allowed */
+    uint32_t salt;    /* mixed into the direction hash: successive calls with
+                         different salts give independent directions, so a caller
+                         can average them while the camera rests */
+    uint32_t flags;   /* 0; unknown bits: RT_E_INVALID */
+} rt_ao_params;
+typedef struct rt_ao_out {
+    void* dev_ao;        /* W*H float, or NULL: (rays - occluded) * (1.0f / rays); a miss pixel 1.0f */
+    void* dev_occluded;  /* W*H uint32, or NULL: occluded count, 0..rays; a miss pixel 0 */
+} rt_ao_out;
+/* stream, ordering and asynchrony as rt_render_gbuffer.  With stats:
+ * primary_rays = W*H, shadow_rays = the AO rays cast (rays x hit pixels),
+ * nodes_visited / prims_tested = the primary walk once per pixel plus every AO
+ * ray's any-hit walk, ms = device time of the launch, the rest 0.  No scene:
+ * RT_E_NOSCENE.  NULL p or out, both buffers NULL, rays not one of the seven
+ * values, radius NaN or <= 0, or unknown flags: RT_E_INVALID.  Reads scene and
+ * camera state only: it never changes a frame.  A multi-device handle answers
+ * from devices[0] with the whole frame. */
+int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, void* stream, rt_stats* stats);
 
 /* ---- one process, several devices (SURVEY 8b B2 "device ids", 8e E1) ------ */
 /* A renderer handle that renders every frame across n_devices GPUs of this

@@ -242,6 +242,15 @@ public:
         const rt_gbuffer g{dev_hits, dev_normals, dev_albedo};
         check(rt_render_gbuffer(r_, &g, stream, stats), r_);
     }
+    // ambient-occlusion layer of the current camera (rt_render_ao): `rays` (1, 2,
+    // .. 64) any-hit rays of length `radius` from every hit pixel; W*H float
+    // (1 = open) and W*H uint32 occluded counts in device memory, each optional
+    void renderAO(uint32_t rays, float radius, void* dev_ao, void* dev_occluded = nullptr, uint32_t salt = 0,
+                  void* stream = nullptr, rt_stats* stats = nullptr) {
+        const rt_ao_params p{rays, radius, salt, 0u};
+        const rt_ao_out o{dev_ao, dev_occluded};
+        check(rt_render_ao(r_, &p, &o, stream, stats), r_);
+    }
     rt_scene_info sceneInfo() const {
         rt_scene_info i;
         check(rt_get_scene_info(r_, &i), r_);

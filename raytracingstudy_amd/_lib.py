@@ -222,6 +222,15 @@ class RtGBuffer(ctypes.Structure):
                 ("dev_albedo", ctypes.c_void_p)]
 
 
+class RtAoParams(ctypes.Structure):
+    _fields_ = [("rays", ctypes.c_uint32), ("radius", ctypes.c_float), ("salt", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
+class RtAoOut(ctypes.Structure):
+    _fields_ = [("dev_ao", ctypes.c_void_p), ("dev_occluded", ctypes.c_void_p)]
+
+
 class RtDisplayOps(ctypes.Structure):
     _fields_ = [("map", DISPLAY_MAP), ("unmap", DISPLAY_UNMAP)]
 
@@ -274,6 +283,7 @@ SIGNATURES = {
     "rt_sweep_at": (_int, [_P, _fp, _fp, ctypes.c_float, ctypes.c_float, _u32, ctypes.POINTER(RtHit), _fp]),
     "rt_pick_thick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
     "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
+    "rt_render_ao": (_int, [_P, ctypes.POINTER(RtAoParams), ctypes.POINTER(RtAoOut), _P, ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),
     "rt_readback": (_int, [_P, _P, _P]),

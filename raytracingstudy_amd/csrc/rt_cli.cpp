@@ -9,6 +9,7 @@
 //           --depth D] [--frames F] [--out image.ppm] [--scene in.rtsph]
 //          [--save-scene out.rtsph] [--host-build] [--gpus N [--same-device]]
 //          [--progressive] [--panel] [--walk] [--test-poison] [--gbuffer hits.bin]
+//          [--ao ao.pgm [--ao-rays R] [--ao-radius X]]
 //
 // --panel prints the stats panel (rt_camera.hpp StatsPanel: the reference's
 // ImGui window numbers plus Mrays/s, spp, GPUs) after every frame; --walk
@@ -16,6 +17,9 @@
 // --progressive accumulates samples while the camera stays put.  --gbuffer
 // renders the first-hit G-buffer of the last frame's camera (rt_render_gbuffer)
 // and writes its hits as W*H raw little-endian rt_hit records {f32 t, u32 sphere}.
+// --ao renders that camera's ambient-occlusion layer (rt_render_ao; R rays a
+// pixel, default 16, of length X, default 0.1) and writes it as a binary PGM,
+// 255 = open.
 //
 // --gpus N: one process drives N devices through the C-ABI's
 // multi-device handle (rt_create_multi): device k renders the 64x64 tiles
@@ -108,7 +112,9 @@ int run_multi(const rt_config& rc, const float pose[16], int gpus, bool same_dev
 }
 
 int main(int argc, char** argv) {
-    std::string cfg = "c2", out, scene_in, scene_out, gbuffer_out;
+    std::string cfg = "c2", out, scene_in, scene_out, gbuffer_out, ao_out;
+    int ao_rays = 16;
+    float ao_radius = 0.1f;
     bool host_build = false, same_device = false, progressive = false, panel = false,
          walk = false, poison = false;
     int gpus = 1;
@@ -135,6 +141,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--scene")) scene_in = next("--scene");
         else if (!strcmp(argv[i], "--save-scene")) scene_out = next("--save-scene");
         else if (!strcmp(argv[i], "--gbuffer")) gbuffer_out = next("--gbuffer");
+        else if (!strcmp(argv[i], "--ao")) ao_out = next("--ao");
+        else if (!strcmp(argv[i], "--ao-rays")) ao_rays = atoi(next("--ao-rays"));
+        else if (!strcmp(argv[i], "--ao-radius")) ao_radius = (float)atof(next("--ao-radius"));
         else if (!strcmp(argv[i], "--host-build")) host_build = true;
         else if (!strcmp(argv[i], "--gpus")) gpus = atoi(next("--gpus")), multi = true;
         else if (!strcmp(argv[i], "--same-device")) same_device = true;
@@ -206,6 +215,7 @@ int main(int argc, char** argv) {
             if (gpus < 1 || gpus > RT_MAX_DEVICES) throw rtamd::Error(RT_E_INVALID, "--gpus must be 1..16");
             if (!scene) throw rtamd::Error(RT_E_INVALID, "--gpus needs a scene config");
             if (!gbuffer_out.empty()) throw rtamd::Error(RT_E_INVALID, "--gbuffer is single-device here");
+            if (!ao_out.empty()) throw rtamd::Error(RT_E_INVALID, "--ao is single-device here");
             return run_multi(rc, pose, gpus, same_device, frames, out, W, H, spp, depth, n,
                              scene_in);
         }
@@ -277,6 +287,40 @@ int main(int argc, char** argv) {
             }
             fclose(f);
             printf("gbuffer: %zu of %zu pixels hit a sphere\n", n_hit, npix);
+        }
+        if (!ao_out.empty()) {
+            // after the last frame: the occlusion layer of the camera it used
+            if (!scene) throw rtamd::Error(RT_E_INVALID, "--ao needs a scene config");
+            const size_t npix = (size_t)W * H;
+            void* d_occ = nullptr;
+            if (hipMalloc(&d_occ, npix * sizeof(uint32_t)) != hipSuccess)
+                throw rtamd::Error(RT_E_HIP, "hipMalloc of the occlusion buffer");
+            std::vector<uint32_t> occ(npix);
+            rt_stats ast{};
+            try {
+                r.renderAO((uint32_t)ao_rays, ao_radius, nullptr, d_occ, 0, nullptr, &ast);
+            } catch (...) {
+                (void)hipFree(d_occ);
+                throw;
+            }
+            const hipError_t e = hipMemcpy(occ.data(), d_occ, npix * sizeof(uint32_t), hipMemcpyDeviceToHost);
+            (void)hipFree(d_occ);
+            if (e != hipSuccess) throw rtamd::Error(RT_E_HIP, "hipMemcpy of the occlusion buffer");
+            std::vector<uint8_t> grey(npix);
+            unsigned long long total = 0;
+            for (size_t i = 0; i < npix; ++i) {
+                total += occ[i];
+                grey[i] = (uint8_t)(((uint32_t)ao_rays - occ[i]) * 255u / (uint32_t)ao_rays);
+            }
+            FILE* f = fopen(ao_out.c_str(), "wb");
+            if (!f || fprintf(f, "P5\n%d %d\n255\n", W, H) < 0 || fwrite(grey.data(), 1, npix, f) != npix) {
+                fprintf(stderr, "cannot write %s\n", ao_out.c_str());
+                if (f) fclose(f);
+                return 1;
+            }
+            fclose(f);
+            printf("ao: %llu of %llu rays occluded (%d rays a pixel, radius %g), %.3f ms\n", total,
+                   (unsigned long long)ast.shadow_rays, ao_rays, ao_radius, ast.ms);
         }
     } catch (const rtamd::Error& e) {
         fprintf(stderr, "rt_cli: %s (code %d)\n", e.what(), e.code);

@@ -80,6 +80,10 @@ hipError_t launch_sweep(const FrameArgs& a, const void* rays, const void* radii,
 // rt_gbuffer.hip: the first-hit G-buffer of a.cam at a.W x a.H against a.sc; null buffers are skipped
 hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* albedo,
                           unsigned long long* counters, hipStream_t st);
+// rt_ao.hip: the ambient-occlusion layer of a.cam at a.W x a.H against a.sc: `rays` (1, 2, .. 64) any-hit rays
+// of length `radius` per hit pixel, directions keyed by `key` (rt_ao_math.h ao_key); null buffers are skipped
+hipError_t launch_ao(const FrameArgs& a, void* ao, void* occluded, uint32_t rays, float radius, uint32_t key,
+                     unsigned long long* counters, hipStream_t st);
 
 // screen_bins.hip: the per-frame screen-space bins
 struct BinBuild {

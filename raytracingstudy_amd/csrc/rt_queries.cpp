@@ -1,13 +1,15 @@
 // rt_queries.cpp — the calls that read a scene without rendering a frame
 // (DESIGN.md 5.7): ray, multi-hit, sphere-overlap, closest-sphere and
-// swept-sphere queries, their single-item wrappers, the first-hit G-buffer.  The reference has none
+// swept-sphere queries, their single-item wrappers, the first-hit G-buffer and the
+// ambient-occlusion layer.  The reference has none
 // (Octree::traverse is a stub, include/octree.h:19-21; its render kernel
 // writes one colour per pixel, src/renderer.cu:57-82).  A query reads scene
-// (the G-buffer: and camera) state only: it takes no frame id, leaves the
+// (the G-buffer and the AO layer: and camera) state only: it takes no frame id, leaves the
 // progressive sums, the frames' counter sets and the qerr word alone, and is
 // ordered after the handle's earlier work like every launch.  Each entry point
 // checks its own arguments in its own order (rt.h states the codes); what
 // follows the checks is stated once, in query_begin and query_launch.
+#include "rt_ao_math.h"
 #include "rt_host.h"
 
 using namespace rtamd;
@@ -392,6 +394,41 @@ int rt_render_gbuffer(rt_renderer* r, const rt_gbuffer* out, void* stream, rt_st
         return launch_gbuffer(a, out->dev_hits, out->dev_normals, out->dev_albedo, ctr, hs);
     });
     if (!st && stats) stats->primary_rays = static_cast<uint64_t>(r->W) * r->H;
+    return st;
+}
+
+// The ambient-occlusion layer of the current camera: like the
+// G-buffer, no fill_frame_args and nothing of the frames' framebuffer.
+int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_render_ao: null handle");
+    if (!p) return fail(r, RT_E_INVALID, "rt_render_ao: null parameters");
+    if (!out || (!out->dev_ao && !out->dev_occluded))
+        return fail(r, RT_E_INVALID, "rt_render_ao: no output buffer");
+    if (!ao_rays_ok(p->rays)) return fail(r, RT_E_INVALID, "rt_render_ao: rays must be 1, 2, 4, 8, 16, 32 or 64");
+    if (!ao_radius_ok(p->radius)) return fail(r, RT_E_INVALID, "rt_render_ao: radius must be > 0");
+    if (p->flags) return fail(r, RT_E_INVALID, "rt_render_ao: unknown flag bits");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_render_ao: no scene (rt_set_scene first)");
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    fill_camera(r, a.cam);
+    a.W = r->W;
+    a.H = r->H;
+    // the frames' seed word (fill_frame_args' seedmix) under the caller's salt
+    const uint32_t key = ao_key(mix32(r->cfg.seed ^ 0x9E3779B9u), p->salt);
+    st = query_launch(r, "rt_render_ao", hs, stats, [&](unsigned long long* ctr) {
+        return launch_ao(a, out->dev_ao, out->dev_occluded, p->rays, p->radius, key, ctr, hs);
+    });
+    if (!st && stats) {
+        stats->primary_rays = static_cast<uint64_t>(r->W) * r->H;
+        // the AO rays cast (rays x hit pixels) are the kernel's count, word 1 of the stat lines
+        // query_launch just read (the stats path has waited for the launch); no other query writes it
+        unsigned long long lines[kStatLineWords], c[4];
+        RT_HIP(r, hipMemcpy(lines, r->q.counters.p, sizeof(lines), hipMemcpyDeviceToHost));
+        sum_stat_lines(lines, c);
+        stats->shadow_rays = c[1];
+    }
     return st;
 }
 

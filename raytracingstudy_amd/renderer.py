@@ -670,6 +670,39 @@ class KernelRenderer:
             out["stats"] = st
         return out
 
+    # -- ambient-occlusion layer (rt_render_ao) -------------------------------------
+    def render_ao_device(self, rays: int, radius: float, ao_ptr: Optional[int] = None,
+                         occluded_ptr: Optional[int] = None, salt: int = 0, stream: Optional[int] = None,
+                         stats: bool = False) -> Optional[RtStats]:
+        """rt_render_ao into buffers already on the GPU, each optional, in frame
+        layout (pixel y*W + x): W*H float32 at ao_ptr (1 = open, a miss 1), W*H
+        uint32 occluded counts at occluded_ptr.  `rays` (1, 2, 4, .. 64) any-hit
+        rays of length `radius` from every hit pixel.  Asynchronous on `stream`
+        (None: the renderer's own) unless stats."""
+        p = _lib.RtAoParams(int(rays), float(radius), int(salt) & 0xFFFFFFFF, 0)
+        o = _lib.RtAoOut(ao_ptr or None, occluded_ptr or None)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_render_ao(self._h, ctypes.byref(p), ctypes.byref(o), _ptr(stream), st_arg), self._h)
+        return st
+
+    def render_ao(self, rays: int, radius: float, salt: int = 0, stats: bool = False) -> dict:
+        """The ambient-occlusion layer of the current size and camera as host arrays:
+        {"ao": (H, W) float32, "occluded": (H, W) uint32[, "stats": RtStats]}.
+        A pixel that hits nothing has ao = 1 and occluded = 0.  Different salts
+        give independent directions: average the layers while the camera rests."""
+        import torch
+        w, h = self.width, self.height
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_ao = torch.empty((h, w), dtype=torch.float32, device=dev)
+        d_occ = torch.empty((h, w), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the allocations are torch's
+        st = self.render_ao_device(rays, radius, d_ao.data_ptr(), d_occ.data_ptr(), salt, None, stats)
+        self.synchronize()
+        out = {"ao": d_ao.cpu().numpy(), "occluded": d_occ.cpu().numpy().view(np.uint32)}
+        if stats:
+            out["stats"] = st
+        return out
+
     def reset_accumulation(self) -> None:
         """Progressive mode: the next frame starts from zero samples."""
         check(self._lib.rt_reset_accumulation(self._h), self._h)
