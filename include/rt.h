@@ -39,7 +39,7 @@
  *   (none: as above; one hit was the most a ray           rt_trace_rays_multi / rt_pick_multi
  *     could report)
  *   (none: one colour per pixel,                          rt_render_gbuffer, rt_render_ao
- *     src/renderer.cu:57-82)
+ *     src/renderer.cu:57-82)                              rt_filter_layer, rt_apply_layer
  *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
  *     the octree which spheres touch a ball)
  *   (none: as above; nothing asks which spheres are       rt_query_closest / rt_closest_at
@@ -695,6 +695,60 @@ typedef struct rt_ao_out {
  * camera state only: it never changes a frame.  A multi-device handle answers
  * from devices[0] with the whole frame. */
 int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, void* stream, rt_stats* stats);
+
+/* ---- guide-driven layer filter, and a layer applied to a frame ------------ */
+/* What makes a cheap layer displayable: an edge-avoiding a-trous filter over any
+ * per-pixel float layer (rt_render_ao's dev_ao at 4 rays; a float4 radiance
+ * layer), steered by the G-buffer's depth and normals, and the multiply of a
+ * layer into an RGBA8 frame.  The reference has no counterpart.
+ * guides: dev_hits and dev_normals as rt_render_gbuffer wrote them for the
+ * handle's current size, both required (a hit's t is finite); dev_albedo is
+ * ignored.  dev_in and dev_out: W*H*channels floats each (channels 4: 16-byte
+ * aligned), distinct; dev_in is never written, every element of dev_out is.
+ * Exactly in f32, no contraction, IEEE division: pixel q is a
+ * miss iff its rt_hit.sphere == RT_NO_HIT; t_q and n_q are a hit's rt_hit.t and
+ * the first three floats of its normal.  Pass s (0-based) reads pass s - 1's
+ * output (pass 0: dev_in) with step = 1 << s.  A miss pixel copies its value.  A
+ * hit pixel p = (x, y) starts from sw = 0, sv[c] = 0 and visits the 25 taps
+ * q = (x + i*step, y + j*step), j = -2..2 outer, i = -2..2 inner, the centre by
+ * the same formula; a tap outside the image or a miss tap is skipped; otherwise
+ *   k  = K[|i|] * K[|j|], K = {0.375f, 0.25f, 0.0625f}
+ *   dn = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+ *   wn = fmaxf(dn, 0.0f), then wn = wn * wn repeated normal_power times
+ *   e  = (t_q - t_p) * iz, iz = 1.0f / (depth_sigma * t_p) once per pixel
+ *   wz = 1.0f / (1.0f + e*e);  w = (k * wn) * wz
+ *   sw += w;  sv[c] += w * v_q[c] in channel order
+ * and the output is sw > 0.0f ? sv[c] / sw : v_p[c] (false for a NaN: garbage
+ * guides copy the value).  NaN and infinite layer values propagate as the
+ * arithmetic says. */
+typedef struct rt_filter_params {
+    uint32_t passes;        /* 1..5; pass s (0-based) uses tap spacing 2^s */
+    uint32_t channels;      /* 1 (e.g. rt_render_ao's dev_ao) or 4 (float4, e.g. radiance) */
+    float    depth_sigma;   /* relative depth tolerance, > 0; +inf: depth ignored */
+    uint32_t normal_power;  /* 0..7: normal weight = max(n.n', 0)^(2^normal_power) */
+    uint32_t flags;         /* 0; unknown bits RT_E_INVALID */
+} rt_filter_params;
+void rt_filter_params_default(rt_filter_params*);   /* passes 3, channels 1, depth_sigma 0.05f, normal_power 5 */
+/* stream, ordering and asynchrony as rt_render_gbuffer.  With stats: ms = device
+ * time of the guide packing and all passes, every counter 0.  NULL p, guides,
+ * dev_in or dev_out, a missing guide buffer, dev_in == dev_out, passes outside
+ * 1..5, channels not 1 or 4, depth_sigma NaN or <= 0, normal_power > 7 or
+ * unknown flags: RT_E_INVALID, and nothing is launched.  Needs no scene.  Reads
+ * the handle's size only: it never changes a frame, its progressive sums or the
+ * counters.  The packed guides and one scratch layer are the handle's own (they
+ * grow with the size and are released by rt_destroy).  A multi-device handle
+ * runs it on devices[0]. */
+int rt_filter_layer(rt_renderer* r, const rt_filter_params* p, const rt_gbuffer* guides,
+                    const void* dev_in, void* dev_out, void* stream, rt_stats* stats);
+/* Multiplies a W*H float layer into W*H packed RGBA8 pixels in place, one pass:
+ * m = floor + (1.0f - floor) * layer (one multiply, then one add); each of R, G
+ * and B becomes (uint8_t)fminf((float)c * m, 255.0f), truncated like the frames'
+ * own conversion (a negative product stores 0); A is unchanged.  dev_rgba8 NULL:
+ * the handle's internal framebuffer.  A bound display is never mapped: pass its
+ * mapped pointer.  floor NaN or outside [0, 1], or a NULL layer: RT_E_INVALID.
+ * Stream and ordering as above.  Only the given buffer is modified: a
+ * progressive handle's sums are not, so the next rt_render overwrites the result. */
+int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float floor, void* stream);
 
 /* ---- one process, several devices (SURVEY 8b B2 "device ids", 8e E1) ------ */
 /* A renderer handle that renders every frame across n_devices GPUs of this

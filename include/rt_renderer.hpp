@@ -251,6 +251,20 @@ public:
         const rt_ao_out o{dev_ao, dev_occluded};
         check(rt_render_ao(r_, &p, &o, stream, stats), r_);
     }
+    // guide-driven filter of a per-pixel layer (rt_filter_layer): W*H*channels floats
+    // from dev_in to dev_out, steered by renderGBuffer's hits and normals
+    void filterLayer(const void* dev_in, void* dev_out, const void* dev_hits, const void* dev_normals,
+                     uint32_t passes = 3, uint32_t channels = 1, float depth_sigma = 0.05f,
+                     uint32_t normal_power = 5, void* stream = nullptr, rt_stats* stats = nullptr) {
+        const rt_filter_params p{passes, channels, depth_sigma, normal_power, 0u};
+        const rt_gbuffer g{const_cast<void*>(dev_hits), const_cast<void*>(dev_normals), nullptr};
+        check(rt_filter_layer(r_, &p, &g, dev_in, dev_out, stream, stats), r_);
+    }
+    // a W*H float layer multiplied into RGBA8 pixels in place (rt_apply_layer):
+    // m = floor + (1 - floor) * layer; dev_rgba8 null: the internal framebuffer
+    void applyLayer(const void* dev_layer, float floor = 0.0f, void* dev_rgba8 = nullptr, void* stream = nullptr) {
+        check(rt_apply_layer(r_, dev_rgba8, dev_layer, floor, stream), r_);
+    }
     rt_scene_info sceneInfo() const {
         rt_scene_info i;
         check(rt_get_scene_info(r_, &i), r_);

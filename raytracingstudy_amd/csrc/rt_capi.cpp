@@ -276,6 +276,7 @@ int rt_destroy(rt_renderer* r) {
     r->prim_shd8.buf.release();
     r->d_shd_rr.release();
     r->q.release();
+    r->flt.release();
     r->sb_order.release();
     r->gpu_build.release();
     r->cell_table.release();

@@ -9,7 +9,7 @@
 //           --depth D] [--frames F] [--out image.ppm] [--scene in.rtsph]
 //          [--save-scene out.rtsph] [--host-build] [--gpus N [--same-device]]
 //          [--progressive] [--panel] [--walk] [--test-poison] [--gbuffer hits.bin]
-//          [--ao ao.pgm [--ao-rays R] [--ao-radius X]]
+//          [--ao ao.pgm [--ao-rays R] [--ao-radius X] [--ao-filter PASSES]]
 //
 // --panel prints the stats panel (rt_camera.hpp StatsPanel: the reference's
 // ImGui window numbers plus Mrays/s, spp, GPUs) after every frame; --walk
@@ -19,7 +19,9 @@
 // and writes its hits as W*H raw little-endian rt_hit records {f32 t, u32 sphere}.
 // --ao renders that camera's ambient-occlusion layer (rt_render_ao; R rays a
 // pixel, default 16, of length X, default 0.1) and writes it as a binary PGM,
-// 255 = open.
+// 255 = open.  --ao-filter PASSES (1..5) filters the layer under the G-buffer's
+// guides first (rt_filter_layer at its default tolerances) and writes the
+// filtered layer instead, (uint8)(value * 255).
 //
 // --gpus N: one process drives N devices through the C-ABI's
 // multi-device handle (rt_create_multi): device k renders the 64x64 tiles
@@ -113,7 +115,7 @@ int run_multi(const rt_config& rc, const float pose[16], int gpus, bool same_dev
 
 int main(int argc, char** argv) {
     std::string cfg = "c2", out, scene_in, scene_out, gbuffer_out, ao_out;
-    int ao_rays = 16;
+    int ao_rays = 16, ao_filter = 0;
     float ao_radius = 0.1f;
     bool host_build = false, same_device = false, progressive = false, panel = false,
          walk = false, poison = false;
@@ -144,6 +146,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ao")) ao_out = next("--ao");
         else if (!strcmp(argv[i], "--ao-rays")) ao_rays = atoi(next("--ao-rays"));
         else if (!strcmp(argv[i], "--ao-radius")) ao_radius = (float)atof(next("--ao-radius"));
+        else if (!strcmp(argv[i], "--ao-filter")) ao_filter = atoi(next("--ao-filter"));
         else if (!strcmp(argv[i], "--host-build")) host_build = true;
         else if (!strcmp(argv[i], "--gpus")) gpus = atoi(next("--gpus")), multi = true;
         else if (!strcmp(argv[i], "--same-device")) same_device = true;
@@ -292,25 +295,45 @@ int main(int argc, char** argv) {
             // after the last frame: the occlusion layer of the camera it used
             if (!scene) throw rtamd::Error(RT_E_INVALID, "--ao needs a scene config");
             const size_t npix = (size_t)W * H;
-            void* d_occ = nullptr;
-            if (hipMalloc(&d_occ, npix * sizeof(uint32_t)) != hipSuccess)
-                throw rtamd::Error(RT_E_HIP, "hipMalloc of the occlusion buffer");
+            // the counts; with --ao-filter also the float layer, the G-buffer's guides and the filtered layer
+            struct DevBufs {
+                void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+                ~DevBufs() {
+                    for (void* q : p)
+                        if (q) (void)hipFree(q);
+                }
+            } d;
+            enum { kOcc, kAo, kHits, kNormals, kFiltered };
+            const size_t bytes[5] = {npix * sizeof(uint32_t), npix * sizeof(float), npix * sizeof(rt_hit),
+                                     npix * 4 * sizeof(float), npix * sizeof(float)};
+            for (int b = 0; b < (ao_filter ? 5 : 1); ++b)
+                if (hipMalloc(&d.p[b], bytes[b]) != hipSuccess)
+                    throw rtamd::Error(RT_E_HIP, "hipMalloc of the occlusion buffers");
             std::vector<uint32_t> occ(npix);
-            rt_stats ast{};
-            try {
-                r.renderAO((uint32_t)ao_rays, ao_radius, nullptr, d_occ, 0, nullptr, &ast);
-            } catch (...) {
-                (void)hipFree(d_occ);
-                throw;
+            std::vector<float> filtered(ao_filter ? npix : 0);
+            rt_stats ast{}, fst{};
+            if (ao_filter) r.renderGBuffer(d.p[kHits], d.p[kNormals], nullptr);
+            r.renderAO((uint32_t)ao_rays, ao_radius, d.p[kAo], d.p[kOcc], 0, nullptr, &ast);
+            if (ao_filter) {
+                rt_filter_params fp;
+                rt_filter_params_default(&fp);
+                r.filterLayer(d.p[kAo], d.p[kFiltered], d.p[kHits], d.p[kNormals], (uint32_t)ao_filter, fp.channels,
+                              fp.depth_sigma, fp.normal_power, nullptr, &fst);
+                if (hipMemcpy(filtered.data(), d.p[kFiltered], bytes[kFiltered], hipMemcpyDeviceToHost) != hipSuccess)
+                    throw rtamd::Error(RT_E_HIP, "hipMemcpy of the filtered layer");
             }
-            const hipError_t e = hipMemcpy(occ.data(), d_occ, npix * sizeof(uint32_t), hipMemcpyDeviceToHost);
-            (void)hipFree(d_occ);
-            if (e != hipSuccess) throw rtamd::Error(RT_E_HIP, "hipMemcpy of the occlusion buffer");
+            if (hipMemcpy(occ.data(), d.p[kOcc], bytes[kOcc], hipMemcpyDeviceToHost) != hipSuccess)
+                throw rtamd::Error(RT_E_HIP, "hipMemcpy of the occlusion buffer");
             std::vector<uint8_t> grey(npix);
             unsigned long long total = 0;
             for (size_t i = 0; i < npix; ++i) {
                 total += occ[i];
-                grey[i] = (uint8_t)(((uint32_t)ao_rays - occ[i]) * 255u / (uint32_t)ao_rays);
+                if (ao_filter) {
+                    const float g = filtered[i] * 255.0f;
+                    grey[i] = g >= 255.0f ? 255 : g > 0.0f ? (uint8_t)g : 0;
+                } else {
+                    grey[i] = (uint8_t)(((uint32_t)ao_rays - occ[i]) * 255u / (uint32_t)ao_rays);
+                }
             }
             FILE* f = fopen(ao_out.c_str(), "wb");
             if (!f || fprintf(f, "P5\n%d %d\n255\n", W, H) < 0 || fwrite(grey.data(), 1, npix, f) != npix) {
@@ -321,6 +344,7 @@ int main(int argc, char** argv) {
             fclose(f);
             printf("ao: %llu of %llu rays occluded (%d rays a pixel, radius %g), %.3f ms\n", total,
                    (unsigned long long)ast.shadow_rays, ao_rays, ao_radius, ast.ms);
+            if (ao_filter) printf("ao-filter: %d passes, %.3f ms\n", ao_filter, fst.ms);
         }
     } catch (const rtamd::Error& e) {
         fprintf(stderr, "rt_cli: %s (code %d)\n", e.what(), e.code);

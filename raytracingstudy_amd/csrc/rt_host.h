@@ -6,7 +6,8 @@
 //   rt_frame.cpp  per-frame preparation and launch (do_render's steps: it plans a
 //                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
-//   rt_queries.cpp    ray, multi-hit, overlap, closest-sphere and swept-sphere queries, picking, the G-buffer
+//   rt_queries.cpp    ray, multi-hit, overlap, closest-sphere and swept-sphere queries, picking, the G-buffer,
+//                     the AO layer, the layer filter and the layer multiply
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -84,6 +85,15 @@ hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* a
 // of length `radius` per hit pixel, directions keyed by `key` (rt_ao_math.h ao_key); null buffers are skipped
 hipError_t launch_ao(const FrameArgs& a, void* ao, void* occluded, uint32_t rays, float radius, uint32_t key,
                      unsigned long long* counters, hipStream_t st);
+// rt_filter.hip: the guide-driven filter of a W x H layer of `channels` floats a pixel (rt_filter_math.h: the
+// parameters, which the caller checked, and the pass plan): packs hits and normals into `rec` (W*H), then `passes`
+// passes from `in` to `out` through `pong` (as large as the layer; may be null for one pass)
+hipError_t launch_filter(uint32_t W, uint32_t H, const void* hits, const void* normals, float4* rec, const void* in,
+                         void* out, float* pong, uint32_t passes, uint32_t channels, float depth_sigma,
+                         uint32_t normal_power, hipStream_t st);
+// ... and the multiply of a W x H layer into packed RGBA8 pixels in place: m = floor + (1 - floor) * layer
+hipError_t launch_apply_layer(uint32_t* rgba8, const float* layer, uint32_t W, uint32_t H, float floor,
+                              hipStream_t st);
 
 // screen_bins.hip: the per-frame screen-space bins
 struct BinBuild {
@@ -298,6 +308,18 @@ struct QueryScratch {
     }
 };
 
+// rt_filter_layer's scratch: the packed guide records of the last call's size and the
+// one layer the passes alternate with the caller's output.  Like QueryScratch it
+// only grows and is released with the handle.
+struct FilterScratch {
+    DevBuf<float4> rec;   // W*H x {n.x, n.y, n.z, t}
+    DevBuf<float> pong;   // W*H*channels
+    void release() {
+        rec.release();
+        pong.release();
+    }
+};
+
 // what an rt_renderer holds (the C-ABI's opaque struct, below, is exactly this)
 struct RendererState {
     rt_config cfg;
@@ -412,6 +434,7 @@ struct RendererState {
     double occ_M = 0.0;
     ScreenBinState bins;
     QueryScratch q;
+    FilterScratch flt;
     rt_scene_info info{};
     std::string err;
     // multi-device handle (rt_create_multi): this renderer is devices[0]'s

@@ -8,23 +8,32 @@
 // progressive sums, the frames' counter sets and the qerr word alone, and is
 // ordered after the handle's earlier work like every launch.  Each entry point
 // checks its own arguments in its own order (rt.h states the codes); what
-// follows the checks is stated once, in query_begin and query_launch.
+// follows the checks is stated once, in query_begin and query_launch.  The two
+// layer calls at the end (rt_filter_layer, rt_apply_layer) read
+// no scene at all, only the handle's size; they share the stream ordering and
+// the stats bracket.
 #include "rt_ao_math.h"
+#include "rt_filter_math.h"
 #include "rt_host.h"
 
 using namespace rtamd;
 
 namespace {
 
-// The device, the stream (the caller's, or the handle's own), the ordering
-// after the handle's last work, and the kernels' leading argument: a FrameArgs
+// The device, the stream (the caller's, or the handle's own) and the ordering
+// after the handle's last work (stream_begin: all the layer calls need), and
+// the query kernels' leading argument: a FrameArgs
 // (kernargs() reinterprets the argument segment as one, rt_query.hip) holding
 // the scene, the rest zero.
-int query_begin(rt_renderer* r, void* stream, hipStream_t& hs, FrameArgs& a) {
+int stream_begin(rt_renderer* r, void* stream, hipStream_t& hs) {
     int st;
     if ((st = set_device(r))) return st;
     hs = stream ? static_cast<hipStream_t>(stream) : own_stream(r);
-    if ((st = order_after_last(r, hs))) return st;
+    return order_after_last(r, hs);
+}
+int query_begin(rt_renderer* r, void* stream, hipStream_t& hs, FrameArgs& a) {
+    int st;
+    if ((st = stream_begin(r, stream, hs))) return st;
     memset(&a, 0, sizeof(a));
     a.sc = r->sc;
     return RT_OK;
@@ -430,6 +439,62 @@ int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, vo
         stats->shadow_rays = c[1];
     }
     return st;
+}
+
+void rt_filter_params_default(rt_filter_params* p) {
+    if (!p) return;
+    p->passes = 3;
+    p->channels = 1;
+    p->depth_sigma = 0.05f;
+    p->normal_power = 5;
+    p->flags = 0;
+}
+
+// The guide-driven filter of a per-pixel layer.  It reads the
+// handle's size and nothing else of it: no scene, no camera, no frame.  The
+// stats bracket is the queries' (its stat lines stay zero: no kernel here counts).
+int rt_filter_layer(rt_renderer* r, const rt_filter_params* p, const rt_gbuffer* guides, const void* dev_in,
+                    void* dev_out, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_filter_layer: null handle");
+    if (!p) return fail(r, RT_E_INVALID, "rt_filter_layer: null parameters");
+    if (!guides || !guides->dev_hits || !guides->dev_normals)
+        return fail(r, RT_E_INVALID, "rt_filter_layer: the hits and the normals of a G-buffer are required");
+    if (!dev_in || !dev_out) return fail(r, RT_E_INVALID, "rt_filter_layer: null layer");
+    if (dev_in == dev_out) return fail(r, RT_E_INVALID, "rt_filter_layer: the input and the output must be distinct");
+    if (!filter_passes_ok(p->passes)) return fail(r, RT_E_INVALID, "rt_filter_layer: passes must be 1..5");
+    if (!filter_channels_ok(p->channels)) return fail(r, RT_E_INVALID, "rt_filter_layer: channels must be 1 or 4");
+    if (!filter_depth_sigma_ok(p->depth_sigma)) return fail(r, RT_E_INVALID, "rt_filter_layer: depth_sigma must be > 0");
+    if (!filter_normal_power_ok(p->normal_power)) return fail(r, RT_E_INVALID, "rt_filter_layer: normal_power must be 0..7");
+    if (p->flags) return fail(r, RT_E_INVALID, "rt_filter_layer: unknown flag bits");
+    hipStream_t hs;
+    int st;
+    if ((st = stream_begin(r, stream, hs))) return st;
+    const size_t n = static_cast<size_t>(r->W) * r->H;
+    if ((st = ensure(r, r->flt.rec, n))) return st;
+    if (filter_needs_scratch(p->passes) && (st = ensure(r, r->flt.pong, n * p->channels))) return st;
+    return query_launch(r, "rt_filter_layer", hs, stats, [&](unsigned long long*) {
+        return launch_filter(r->W, r->H, guides->dev_hits, guides->dev_normals, r->flt.rec.p, dev_in, dev_out,
+                             filter_needs_scratch(p->passes) ? r->flt.pong.p : nullptr, p->passes, p->channels,
+                             p->depth_sigma, p->normal_power, hs);
+    });
+}
+
+// The multiply of a layer into a frame's pixels, in place: the caller's buffer
+// (a mapped display buffer included: this call maps nothing) or the internal
+// framebuffer.  Nothing of the progressive sums: the next frame overwrites it.
+int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float floor, void* stream) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_apply_layer: null handle");
+    if (!dev_layer) return fail(r, RT_E_INVALID, "rt_apply_layer: null layer");
+    if (!apply_floor_ok(floor)) return fail(r, RT_E_INVALID, "rt_apply_layer: floor must be in [0, 1]");
+    uint32_t* px = dev_rgba8 ? static_cast<uint32_t*>(dev_rgba8) : r->fb.p;
+    // (a resize whose allocation failed leaves no internal framebuffer)
+    if (!px) return fail(r, RT_E_STATE, "rt_apply_layer: no framebuffer (a resize failed): resize again");
+    hipStream_t hs;
+    int st;
+    if ((st = stream_begin(r, stream, hs))) return st;
+    return query_launch(r, "rt_apply_layer", hs, nullptr, [&](unsigned long long*) {
+        return launch_apply_layer(px, static_cast<const float*>(dev_layer), r->W, r->H, floor, hs);
+    });
 }
 
 }  // extern "C"

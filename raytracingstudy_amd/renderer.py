@@ -685,23 +685,87 @@ class KernelRenderer:
         check(self._lib.rt_render_ao(self._h, ctypes.byref(p), ctypes.byref(o), _ptr(stream), st_arg), self._h)
         return st
 
-    def render_ao(self, rays: int, radius: float, salt: int = 0, stats: bool = False) -> dict:
+    def render_ao(self, rays: int, radius: float, salt: int = 0, stats: bool = False, filter_passes: int = 0,
+                  depth_sigma: float = 0.05, normal_power: int = 5) -> dict:
         """The ambient-occlusion layer of the current size and camera as host arrays:
         {"ao": (H, W) float32, "occluded": (H, W) uint32[, "stats": RtStats]}.
         A pixel that hits nothing has ao = 1 and occluded = 0.  Different salts
-        give independent directions: average the layers while the camera rests."""
+        give independent directions: average the layers while the camera rests.
+        filter_passes > 0: the G-buffer, the layer and rt_filter_layer over it run
+        on one stream, and "ao_filtered": (H, W) float32 is returned beside the
+        raw layer (what a viewer shows of a 4-ray layer while the camera moves)."""
         import torch
         w, h = self.width, self.height
         dev = torch.device("cuda", self.multi_info()["devices"][0])
         d_ao = torch.empty((h, w), dtype=torch.float32, device=dev)
         d_occ = torch.empty((h, w), dtype=torch.int32, device=dev)
+        if filter_passes:
+            d_hits = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
+            d_nrm = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+            d_flt = torch.empty((h, w), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)  # the allocations are torch's
+        if filter_passes:
+            self.render_gbuffer_device(d_hits.data_ptr(), d_nrm.data_ptr())
         st = self.render_ao_device(rays, radius, d_ao.data_ptr(), d_occ.data_ptr(), salt, None, stats)
+        if filter_passes:
+            self.filter_layer_device(d_ao.data_ptr(), d_flt.data_ptr(), d_hits.data_ptr(), d_nrm.data_ptr(),
+                                     filter_passes, 1, depth_sigma, normal_power)
         self.synchronize()
         out = {"ao": d_ao.cpu().numpy(), "occluded": d_occ.cpu().numpy().view(np.uint32)}
+        if filter_passes:
+            out["ao_filtered"] = d_flt.cpu().numpy()
         if stats:
             out["stats"] = st
         return out
+
+    # -- guide-driven layer filter and layer multiply (rt_filter_layer, rt_apply_layer) ----
+    def filter_layer_device(self, in_ptr: int, out_ptr: int, hits_ptr: int, normals_ptr: int, passes: int = 3,
+                            channels: int = 1, depth_sigma: float = 0.05, normal_power: int = 5,
+                            stream: Optional[int] = None, stats: bool = False) -> Optional[RtStats]:
+        """rt_filter_layer on buffers already on the GPU, in frame layout: W*H*channels
+        float32 from in_ptr to out_ptr (distinct), steered by render_gbuffer_device's
+        W*H rt_hit at hits_ptr and W*H float[4] normals at normals_ptr.  Asynchronous
+        on `stream` (None: the renderer's own) unless stats."""
+        p = _lib.RtFilterParams(int(passes), int(channels), float(depth_sigma), int(normal_power), 0)
+        g = _lib.RtGBuffer(hits_ptr or None, normals_ptr or None, None)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_filter_layer(self._h, ctypes.byref(p), ctypes.byref(g), _ptr(in_ptr), _ptr(out_ptr),
+                                        _ptr(stream), st_arg), self._h)
+        return st
+
+    def filter_layer(self, layer, gbuffer: dict, passes: int = 3, depth_sigma: float = 0.05,
+                     normal_power: int = 5) -> np.ndarray:
+        """A host layer, (H, W) or (H, W, 4) float32, filtered under the guides of
+        `gbuffer` (render_gbuffer's dict: "t", "sphere" and "normal") -> the
+        filtered layer, same shape.  Uploads, runs rt_filter_layer on the handle's
+        first device and waits."""
+        import torch
+        w, h = self.width, self.height
+        a = np.ascontiguousarray(layer, np.float32)
+        if a.shape not in ((h, w), (h, w, 4)):
+            raise ValueError(f"layer must be ({h}, {w}) or ({h}, {w}, 4) float32")
+        hits = np.empty((h, w, 2), np.uint32)
+        hits[..., 0] = np.ascontiguousarray(gbuffer["t"], np.float32).view(np.uint32).reshape(h, w)
+        hits[..., 1] = np.asarray(gbuffer["sphere"], np.uint32).reshape(h, w)
+        nrm = np.ascontiguousarray(gbuffer["normal"], np.float32).reshape(h, w, 4)
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_in = torch.from_numpy(a).to(dev)
+        d_hits = torch.from_numpy(hits.view(np.int32)).to(dev)
+        d_nrm = torch.from_numpy(nrm).to(dev)
+        d_out = torch.empty_like(d_in)
+        torch.cuda.synchronize(dev)  # the uploads ran on torch's stream
+        self.filter_layer_device(d_in.data_ptr(), d_out.data_ptr(), d_hits.data_ptr(), d_nrm.data_ptr(), passes,
+                                 1 if a.ndim == 2 else 4, depth_sigma, normal_power)
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    def apply_layer_device(self, layer_ptr: int, floor: float = 0.0, rgba8_ptr: Optional[int] = None,
+                           stream: Optional[int] = None) -> None:
+        """rt_apply_layer: the W*H float32 layer at layer_ptr multiplied into the W*H
+        RGBA8 pixels at rgba8_ptr (None: the internal framebuffer) in place,
+        m = floor + (1 - floor) * layer; alpha is kept.  Asynchronous on `stream`."""
+        check(self._lib.rt_apply_layer(self._h, _ptr(rgba8_ptr), _ptr(layer_ptr), float(floor), _ptr(stream)),
+              self._h)
 
     def reset_accumulation(self) -> None:
         """Progressive mode: the next frame starts from zero samples."""
