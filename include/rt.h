@@ -40,6 +40,7 @@
  *     could report)
  *   (none: one colour per pixel,                          rt_render_gbuffer, rt_render_ao
  *     src/renderer.cu:57-82)                              rt_filter_layer, rt_apply_layer
+ *   (none: nothing is kept between two frames)            rt_reproject_layer
  *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
  *     the octree which spheres touch a ball)
  *   (none: as above; nothing asks which spheres are       rt_query_closest / rt_closest_at
@@ -749,6 +750,68 @@ int rt_filter_layer(rt_renderer* r, const rt_filter_params* p, const rt_gbuffer*
  * Stream and ordering as above.  Only the given buffer is modified: a
  * progressive handle's sums are not, so the next rt_render overwrites the result. */
 int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float floor, void* stream);
+
+/* A per-pixel layer carried across camera motion: the running mean of a layer
+ * (rt_render_ao's dev_ao at a few rays, salt = the frame number; a float4 radiance
+ * layer) reprojected from the previous camera into the handle's current one, the
+ * one rt_render_gbuffer just used.  The primitives are spheres, so "the same
+ * surface as last frame" is the equality of two sphere indices plus a relative
+ * depth tolerance.  The caller keeps two sets of {hits, layer, count} and swaps
+ * them each frame; the handle keeps nothing.  While the camera rests the result
+ * is the plain mean of the layers (count k + 1 on frame k, up to max_count).
+ * Exactly in f32, in the stated order, no contraction, IEEE division and square
+ * root.  o = pose[3].xyz and d = Camera::getRay(x, y) of the
+ * current camera, exactly rt_render_gbuffer's ray; o', P' = hist->pose and
+ * fx = K'[0], fy = K'[4], cx = K'[2], cy = K'[5] of hist->K.  Per pixel (x, y) with
+ * its current hit {t, s}:
+ *   1. out[c] = cur[c], count = 1.0f for a miss (s == RT_NO_HIT), for hist == NULL
+ *      and where no tap below is accepted.
+ *   2. p = o + t*d (one multiply, then one add);  q = p - o';
+ *      c_x = (P'[0]*q.x + P'[1]*q.y) + P'[2]*q.z, c_y with P'[4..6], c_z with
+ *      P'[8..10] (the rotation block's transpose, used as given);
+ *      dist = sqrtf((q.x*q.x + q.y*q.y) + q.z*q.z);  taps only if c_z > 0.0f
+ *      (false for a NaN).
+ *   3. u = (c_x / c_z) * fx + cx, v = (c_y / c_z) * fy + cy;  u0 = floorf(u),
+ *      v0 = floorf(v), a = u - u0, b = v - v0.
+ *   4. taps (u0 + i, v0 + j), j = 0, 1 outer, i = 0, 1 inner.  A tap is inside iff
+ *      0 <= u0 + i <= W - 1 and 0 <= v0 + j <= H - 1, compared in float (a NaN or a
+ *      huge coordinate is outside).  An inside tap with history hit {t', s'} is
+ *      accepted iff s' == s and fabsf(dist - t') <= depth_tol * t'.  Then
+ *      wx = i ? a : 1.0f - a, wy = j ? b : 1.0f - b, w = wx * wy;
+ *      sw += w;  sv[c] += w * hist_layer[c];  sc += w * hist_count.
+ *   5. if sw > 0.0f: hv[c] = sv[c] / sw, hc = sc / sw, n = fminf(hc + 1.0f,
+ *      max_count), alpha = 1.0f / n, out[c] = hv[c] + (cur[c] - hv[c]) * alpha,
+ *      count = n;  else rule 1.
+ * NaN and infinite layer or count values propagate as the arithmetic says.  The
+ * history assumes a static scene between the two frames. */
+typedef struct rt_history {          /* the previous frame's, all caller-owned, the handle's current size */
+    const void* dev_hits;   /* W*H rt_hit: rt_render_gbuffer's dev_hits under the previous camera */
+    const void* dev_layer;  /* W*H*channels floats: the previous call's dev_out */
+    const void* dev_count;  /* W*H floats: the previous call's dev_count_out */
+    float pose[16];         /* the previous camera, as rt_set_pose / rt_set_intrinsic take them */
+    float K[9];
+} rt_history;
+typedef struct rt_reproject_params {
+    uint32_t channels;   /* 1 or 4 (4: 16-byte aligned layers) */
+    float    max_count;  /* finite, >= 1: the mean's longest memory; 1/max_count is the smallest blend weight */
+    float    depth_tol;  /* > 0, +inf allowed: relative tolerance between the point's distance from the previous camera and the history's t */
+    uint32_t flags;      /* 0; unknown bits RT_E_INVALID */
+} rt_reproject_params;
+void rt_reproject_params_default(rt_reproject_params*);   /* channels 1, max_count 32, depth_tol 0.05f */
+/* stream, ordering and asynchrony as rt_filter_layer.  With stats: ms = device
+ * time of the pass, every counter 0.  A NULL p, dev_hits, dev_cur, dev_out or
+ * dev_count_out, a non-NULL hist with a NULL member buffer, dev_out equal to
+ * dev_cur or to hist->dev_layer, dev_count_out equal to hist->dev_count, channels
+ * not 1 or 4, max_count NaN, infinite or below 1, depth_tol NaN or <= 0, or unknown
+ * flags: RT_E_INVALID, and nothing is launched.  Needs no scene.  Reads the
+ * handle's size and camera only: it never changes a frame, its progressive sums
+ * or the counters.  A multi-device handle runs it on devices[0]. */
+int rt_reproject_layer(rt_renderer* r, const rt_reproject_params* p,
+                       const void* dev_hits,        /* W*H rt_hit: the CURRENT camera's G-buffer hits */
+                       const rt_history* hist,      /* NULL: no history (first frame, after a resize or a scene change) */
+                       const void* dev_cur,         /* W*H*channels: this frame's layer, never written */
+                       void* dev_out, void* dev_count_out,   /* W*H*channels and W*H floats; every element written */
+                       void* stream, rt_stats* stats);
 
 /* ---- one process, several devices (SURVEY 8b B2 "device ids", 8e E1) ------ */
 /* A renderer handle that renders every frame across n_devices GPUs of this

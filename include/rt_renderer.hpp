@@ -265,6 +265,15 @@ public:
     void applyLayer(const void* dev_layer, float floor = 0.0f, void* dev_rgba8 = nullptr, void* stream = nullptr) {
         check(rt_apply_layer(r_, dev_rgba8, dev_layer, floor, stream), r_);
     }
+    // a layer carried across camera motion (rt_reproject_layer): this frame's layer
+    // dev_cur blended with the previous frame's mean, reprojected into the current
+    // camera; hist null: no history (first frame, after a resize or a scene change)
+    void reprojectLayer(const void* dev_hits, const rt_history* hist, const void* dev_cur, void* dev_out,
+                        void* dev_count_out, uint32_t channels = 1, float max_count = 32.0f, float depth_tol = 0.05f,
+                        void* stream = nullptr, rt_stats* stats = nullptr) {
+        const rt_reproject_params p{channels, max_count, depth_tol, 0u};
+        check(rt_reproject_layer(r_, &p, dev_hits, hist, dev_cur, dev_out, dev_count_out, stream, stats), r_);
+    }
     rt_scene_info sceneInfo() const {
         rt_scene_info i;
         check(rt_get_scene_info(r_, &i), r_);

@@ -236,6 +236,16 @@ class RtFilterParams(ctypes.Structure):
                 ("normal_power", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class RtHistory(ctypes.Structure):
+    _fields_ = [("dev_hits", ctypes.c_void_p), ("dev_layer", ctypes.c_void_p), ("dev_count", ctypes.c_void_p),
+                ("pose", ctypes.c_float * 16), ("K", ctypes.c_float * 9)]
+
+
+class RtReprojectParams(ctypes.Structure):
+    _fields_ = [("channels", ctypes.c_uint32), ("max_count", ctypes.c_float), ("depth_tol", ctypes.c_float),
+                ("flags", ctypes.c_uint32)]
+
+
 class RtDisplayOps(ctypes.Structure):
     _fields_ = [("map", DISPLAY_MAP), ("unmap", DISPLAY_UNMAP)]
 
@@ -293,6 +303,9 @@ SIGNATURES = {
     "rt_filter_layer": (_int, [_P, ctypes.POINTER(RtFilterParams), ctypes.POINTER(RtGBuffer), _P, _P, _P,
                                ctypes.POINTER(RtStats)]),
     "rt_apply_layer": (_int, [_P, _P, _P, ctypes.c_float, _P]),
+    "rt_reproject_params_default": (None, [ctypes.POINTER(RtReprojectParams)]),
+    "rt_reproject_layer": (_int, [_P, ctypes.POINTER(RtReprojectParams), _P, ctypes.POINTER(RtHistory), _P, _P, _P, _P,
+                                  ctypes.POINTER(RtStats)]),
     "rt_reset_accumulation": (_int, [_P]),
     "rt_synchronize": (_int, [_P]),
     "rt_readback": (_int, [_P, _P, _P]),

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_filter_math.h"
+#include "rt_layer.h"  // LayerPixel: a layer's pixel as one dword or one dwordx4
 #include "rt_params.h"
 
 namespace rtamd {
@@ -43,27 +44,6 @@ __global__ void __launch_bounds__(kFlatThreads) filter_pack_kernel(const uint2* 
     g.w = h.y == kNoHit ? __builtin_inff() : __uint_as_float(h.x);
     rec[i] = g;
 }
-
-// a layer's pixel as kC floats: one dword or one dwordx4
-template <uint32_t kC>
-struct LayerPixel;
-template <>
-struct LayerPixel<1> {
-    float v[1];
-    __device__ __forceinline__ void load(const float* p, size_t i) { v[0] = p[i]; }
-    __device__ __forceinline__ void store(float* p, size_t i) const { p[i] = v[0]; }
-};
-template <>
-struct alignas(16) LayerPixel<4> {
-    float v[4];
-    __device__ __forceinline__ void load(const float* p, size_t i) {
-        const float4 q = reinterpret_cast<const float4*>(p)[i];
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    }
-    __device__ __forceinline__ void store(float* p, size_t i) const {
-        reinterpret_cast<float4*>(p)[i] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-};
 
 // One pass at tap spacing `step` (here 8 and 16; W, H <= 32768: the tap coordinates fit an int)
 // from global memory.

@@ -7,7 +7,7 @@
 //                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
 //   rt_queries.cpp    ray, multi-hit, overlap, closest-sphere and swept-sphere queries, picking, the G-buffer,
-//                     the AO layer, the layer filter and the layer multiply
+//                     the AO layer, the layer filter, the layer multiply and the layer reprojection
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +26,7 @@
 #include "rt_closest_math.h"
 #include "rt_overlap_math.h"
 #include "rt_params.h"
+#include "rt_reproject_math.h"
 #include "rt_sweep_math.h"
 #include "scene_build.h"
 
@@ -94,6 +95,12 @@ hipError_t launch_filter(uint32_t W, uint32_t H, const void* hits, const void* n
 // ... and the multiply of a W x H layer into packed RGBA8 pixels in place: m = floor + (1 - floor) * layer
 hipError_t launch_apply_layer(uint32_t* rgba8, const float* layer, uint32_t W, uint32_t H, float floor,
                               hipStream_t st);
+// rt_reproject.hip: a W x H layer of `channels` floats a pixel carried from the previous camera `prev` into `cam`
+// (rt_reproject_math.h: the parameters, which the caller checked): `hits` and `cur` of the current frame to `out` and
+// `count_out`; h_hits, h_layer and h_count the previous frame's, h_hits null for no history
+hipError_t launch_reproject(const CamArgs& cam, uint32_t W, uint32_t H, const void* hits, const void* cur, void* out,
+                            void* count_out, const void* h_hits, const void* h_layer, const void* h_count,
+                            const PrevCamera& prev, uint32_t channels, float max_count, float depth_tol, hipStream_t st);
 
 // screen_bins.hip: the per-frame screen-space bins
 struct BinBuild {

@@ -8,10 +8,10 @@
 // progressive sums, the frames' counter sets and the qerr word alone, and is
 // ordered after the handle's earlier work like every launch.  Each entry point
 // checks its own arguments in its own order (rt.h states the codes); what
-// follows the checks is stated once, in query_begin and query_launch.  The two
-// layer calls at the end (rt_filter_layer, rt_apply_layer) read
-// no scene at all, only the handle's size; they share the stream ordering and
-// the stats bracket.
+// follows the checks is stated once, in query_begin and query_launch.  The
+// layer calls at the end (rt_filter_layer, rt_apply_layer; DESIGN.md 5.16;
+// rt_reproject_layer, 5.17) read no scene at all, only the handle's size and,
+// the last, its camera; they share the stream ordering and the stats bracket.
 #include "rt_ao_math.h"
 #include "rt_filter_math.h"
 #include "rt_host.h"
@@ -494,6 +494,48 @@ int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float
     if ((st = stream_begin(r, stream, hs))) return st;
     return query_launch(r, "rt_apply_layer", hs, nullptr, [&](unsigned long long*) {
         return launch_apply_layer(px, static_cast<const float*>(dev_layer), r->W, r->H, floor, hs);
+    });
+}
+
+void rt_reproject_params_default(rt_reproject_params* p) {
+    if (!p) return;
+    p->channels = 1;
+    p->max_count = 32.0f;
+    p->depth_tol = 0.05f;
+    p->flags = 0;
+}
+
+// A layer carried across camera motion: the handle's size and
+// current camera, and the caller's buffers of this frame and the previous one.
+// No scene, no frame; the handle keeps nothing between two calls.
+int rt_reproject_layer(rt_renderer* r, const rt_reproject_params* p, const void* dev_hits, const rt_history* hist,
+                       const void* dev_cur, void* dev_out, void* dev_count_out, void* stream, rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_reproject_layer: null handle");
+    if (!p) return fail(r, RT_E_INVALID, "rt_reproject_layer: null parameters");
+    if (!dev_hits) return fail(r, RT_E_INVALID, "rt_reproject_layer: the current G-buffer's hits are required");
+    if (!dev_cur || !dev_out || !dev_count_out) return fail(r, RT_E_INVALID, "rt_reproject_layer: null layer or count");
+    if (hist && (!hist->dev_hits || !hist->dev_layer || !hist->dev_count))
+        return fail(r, RT_E_INVALID, "rt_reproject_layer: a history needs its hits, its layer and its count");
+    if (dev_out == dev_cur || (hist && dev_out == hist->dev_layer))
+        return fail(r, RT_E_INVALID, "rt_reproject_layer: the output must be distinct from the layers it reads");
+    if (hist && dev_count_out == hist->dev_count)
+        return fail(r, RT_E_INVALID, "rt_reproject_layer: the count output must be distinct from the history's count");
+    if (!reproject_channels_ok(p->channels)) return fail(r, RT_E_INVALID, "rt_reproject_layer: channels must be 1 or 4");
+    if (!reproject_max_count_ok(p->max_count))
+        return fail(r, RT_E_INVALID, "rt_reproject_layer: max_count must be finite and >= 1");
+    if (!reproject_depth_tol_ok(p->depth_tol)) return fail(r, RT_E_INVALID, "rt_reproject_layer: depth_tol must be > 0");
+    if (p->flags) return fail(r, RT_E_INVALID, "rt_reproject_layer: unknown flag bits");
+    hipStream_t hs;
+    int st;
+    if ((st = stream_begin(r, stream, hs))) return st;
+    CamArgs cam;
+    fill_camera(r, cam);
+    PrevCamera prev{};
+    if (hist) prev = prev_camera(hist->pose, hist->K);
+    return query_launch(r, "rt_reproject_layer", hs, stats, [&](unsigned long long*) {
+        return launch_reproject(cam, r->W, r->H, dev_hits, dev_cur, dev_out, dev_count_out,
+                                hist ? hist->dev_hits : nullptr, hist ? hist->dev_layer : nullptr,
+                                hist ? hist->dev_count : nullptr, prev, p->channels, p->max_count, p->depth_tol, hs);
     });
 }
 

@@ -767,6 +767,75 @@ class KernelRenderer:
         check(self._lib.rt_apply_layer(self._h, _ptr(rgba8_ptr), _ptr(layer_ptr), float(floor), _ptr(stream)),
               self._h)
 
+    # -- a layer carried across camera motion (rt_reproject_layer) ----------------------
+    def reproject_layer_device(self, hits_ptr: int, cur_ptr: int, out_ptr: int, count_out_ptr: int,
+                               history: Optional[dict] = None, channels: int = 1, max_count: float = 32.0,
+                               depth_tol: float = 0.05, stream: Optional[int] = None,
+                               stats: bool = False) -> Optional[RtStats]:
+        """rt_reproject_layer on buffers already on the GPU, in frame layout: this
+        frame's W*H*channels float32 layer at cur_ptr, under the current camera's
+        W*H rt_hit at hits_ptr, blended with the previous frame's reprojected mean
+        into out_ptr, the counts (W*H float32) into count_out_ptr.  history: None
+        (no history) or {"hits", "layer", "count": device pointers of the previous
+        frame, "pose": 16 floats, "K": 9 floats: the previous camera}.
+        Asynchronous on `stream` (None: the renderer's own) unless stats."""
+        p = _lib.RtReprojectParams(int(channels), float(max_count), float(depth_tol), 0)
+        h_arg = None
+        if history is not None:
+            pose = np.ascontiguousarray(history["pose"], np.float32).reshape(16)
+            K = np.ascontiguousarray(history["K"], np.float32).reshape(9)
+            h = _lib.RtHistory(history["hits"] or None, history["layer"] or None, history["count"] or None,
+                               (ctypes.c_float * 16)(*pose.tolist()), (ctypes.c_float * 9)(*K.tolist()))
+            h_arg = ctypes.byref(h)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_reproject_layer(self._h, ctypes.byref(p), _ptr(hits_ptr), h_arg, _ptr(cur_ptr),
+                                           _ptr(out_ptr), _ptr(count_out_ptr), _ptr(stream), st_arg), self._h)
+        return st
+
+    def reproject_layer(self, layer, hits, history: Optional[dict] = None, max_count: float = 32.0,
+                        depth_tol: float = 0.05):
+        """Torch tensors on the handle's first device: `layer` (H, W) or (H, W, 4)
+        float32, this frame's; `hits` (H, W, 2) int32, render_gbuffer_device's rt_hit
+        records under the current camera; history: None or {"hits", "layer",
+        "count": the previous frame's tensors (count (H, W) float32), "pose", "K":
+        the previous camera} -> (out, count), new tensors.  Every tensor must be
+        contiguous, of the handle's current size (the history's layer of `layer`'s
+        shape) and on its first device: ValueError otherwise, before anything runs.
+        Runs rt_reproject_layer and waits.  Feed (hits, out, count) and camera() back
+        as the next history."""
+        import torch
+        w, h = self.width, self.height
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+
+        def want(name, a, shapes, dtype):
+            """`a` is a contiguous tensor of one of `shapes` and `dtype` on the handle's first device:
+            anything else would make the kernel read past a buffer's end or another device's memory."""
+            if (not isinstance(a, torch.Tensor) or tuple(a.shape) not in shapes or a.dtype != dtype
+                    or a.device != dev or not a.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape "
+                                 f"{' or '.join(map(str, shapes))} on {dev}")
+
+        want("layer", layer, ((h, w), (h, w, 4)), torch.float32)
+        want("hits", hits, ((h, w, 2),), torch.int32)
+        channels = 1 if layer.dim() == 2 else 4
+        if history is not None:
+            want("history['hits']", history["hits"], ((h, w, 2),), torch.int32)
+            want("history['layer']", history["layer"], (tuple(layer.shape),), torch.float32)
+            want("history['count']", history["count"], ((h, w),), torch.float32)
+            if np.asarray(history["pose"]).size != 16 or np.asarray(history["K"]).size != 9:
+                raise ValueError("history['pose'] must hold 16 floats and history['K'] 9")
+        out = torch.empty_like(layer)
+        count = torch.empty((h, w), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)  # the inputs were made on torch's streams
+        hist = None
+        if history is not None:
+            hist = dict(hits=history["hits"].data_ptr(), layer=history["layer"].data_ptr(),
+                        count=history["count"].data_ptr(), pose=history["pose"], K=history["K"])
+        self.reproject_layer_device(hits.data_ptr(), layer.data_ptr(), out.data_ptr(), count.data_ptr(), hist,
+                                    channels, max_count, depth_tol)
+        self.synchronize()
+        return out, count
+
     def reset_accumulation(self) -> None:
         """Progressive mode: the next frame starts from zero samples."""
         check(self._lib.rt_reset_accumulation(self._h), self._h)
