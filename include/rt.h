@@ -40,6 +40,8 @@
  *     could report)
  *   (none: one colour per pixel,                          rt_render_gbuffer, rt_render_ao
  *     src/renderer.cu:57-82)                              rt_filter_layer, rt_apply_layer
+ *   (none: a hit is lit by one light and a constant       rt_render_indirect, rt_add_layer
+ *     term, src/renderer.cu:57-82)
  *   (none: nothing is kept between two frames)            rt_reproject_layer
  *   (none: Octree::traverse is a stub; nothing asks       rt_query_overlaps / rt_overlaps_at
  *     the octree which spheres touch a ball)
@@ -697,6 +699,60 @@ typedef struct rt_ao_out {
  * from devices[0] with the whole frame. */
 int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, void* stream, rt_stats* stats);
 
+/* ---- one-bounce diffuse light layer ---------------------------------------- */
+/* What the constant ambient term cannot show: the light a hit receives from the
+ * lit spheres around it, and its colour.  rt_render_ao's rays with another
+ * payload: each returns its NEAREST hit shaded as a frame shades a primary hit,
+ * or the frames' miss colour where it escapes, and a pixel stores their mean as
+ * a float4 layer {r, g, b, w} that rt_reproject_layer and rt_filter_layer
+ * (channels = 4) carry and rt_add_layer adds into the frame.
+ * The reference has no counterpart.
+ * Exactly in f32, in the stated order, no contraction, IEEE division and square
+ * root, no transcendental.  Pixel (x, y): the primary ray and
+ * hit are rt_pick(x, y)'s; p = o + t*d, n = (p - c) * (1.0f / r); the bounce
+ * origin is o' = p + n * 1e-5 and ray i's direction d_i is rt_render_ao's (with
+ * equal rays, radius and salt these are its rays bit for bit).  A miss pixel casts
+ * nothing and stores {0, 0, 0, 1.0f} and a count of 0.
+ * Ray i: tmin = 0, tmax = radius, RT_QUERY_NEAREST (smallest t, then smallest
+ * sphere index).
+ *   miss: c_i = {(200.0f/255.0f) * sky_scale, sat(d_i.y) * sky_scale,
+ *         sat(d_i.z) * sky_scale}, sat(x) = x > 0 ? (x < 1 ? x : 1) : 0.
+ *   hit on sphere (c2, r2) with albedo word al at t2:
+ *         q = o' + t2*d_i;  m = (q - c2) * (1.0f / r2);
+ *         ndl = (m.x*L.x + m.y*L.y) + m.z*L.z, L the handle's unit vector toward
+ *         the light (-light_dir / |light_dir|);  lam = ndl > 0 ? ndl : 0;
+ *         if ndl > 0 and the handle has no RT_FLAG_NO_SHADOWS: one RT_QUERY_ANY
+ *         ray from q + m * 1e-5 along L, tmin = 0, tmax = +inf; a hit sets lam = 0;
+ *         f = ambient + (1.0f - ambient) * lam;
+ *         c_i[k] = (float)al_k * (1.0f / 255.0f) * f, al_k the k-th byte of al.
+ * Sum: for m = 1, 2, 4, .. < rays every v[i] becomes v[i] + v[i ^ m] (the frames'
+ * pairing), per channel; rgb = v[0] * (1.0f / rays); w = (float)(rays - hits) *
+ * (1.0f / rays), hits the rays that hit: w has the bits of rt_render_ao's dev_ao
+ * and dev_occluded equals its dev_occluded under equal parameters. */
+typedef struct rt_indirect_params {
+    uint32_t rays;       /* bounce rays per hit pixel: 1, 2, 4, 8, 16, 32 or 64 */
+    float    radius;     /* each bounce ray's tmax in world units: > 0, +inf allowed */
+    uint32_t salt;       /* as rt_ao_params.salt */
+    float    sky_scale;  /* finite, >= 0: what a ray that escapes brings, times the frames' miss colour */
+    uint32_t flags;      /* 0; unknown bits RT_E_INVALID */
+} rt_indirect_params;
+typedef struct rt_indirect_out {
+    void* dev_layer;     /* W*H float[4], 16-byte aligned, or NULL: {r, g, b, w}; a miss pixel {0, 0, 0, 1.0f} */
+    void* dev_occluded;  /* W*H uint32, or NULL: bounce rays that hit something, 0..rays; a miss pixel 0 */
+} rt_indirect_out;
+/* stream, ordering and asynchrony as rt_render_ao.  With stats: primary_rays =
+ * W*H, shadow_rays = the bounce rays cast (rays x hit pixels) plus the shadow
+ * rays cast at their hits, nodes_visited / prims_tested = the primary walk once
+ * per pixel plus every bounce ray's nearest walk plus every such shadow ray's
+ * any-hit walk, ms = device time of the launch, the rest 0.  NULL p or out, both
+ * buffers NULL, rays not one of the seven values, radius NaN or <= 0, sky_scale
+ * NaN, infinite or negative, or unknown flags: RT_E_INVALID, and nothing is
+ * launched.  No scene: RT_E_NOSCENE.  Reads scene and camera state and the
+ * handle's light_dir, ambient and RT_FLAG_NO_SHADOWS only: it never changes a
+ * frame.  A multi-device handle answers from devices[0] with the whole frame. */
+int rt_render_indirect(rt_renderer* r, const rt_indirect_params* p, const rt_indirect_out* out, void* stream,
+                       rt_stats* stats);
+
 /* ---- guide-driven layer filter, and a layer applied to a frame ------------ */
 /* What makes a cheap layer displayable: an edge-avoiding a-trous filter over any
  * per-pixel float layer (rt_render_ao's dev_ao at 4 rays; a float4 radiance
@@ -750,6 +806,22 @@ int rt_filter_layer(rt_renderer* r, const rt_filter_params* p, const rt_gbuffer*
  * Stream and ordering as above.  Only the given buffer is modified: a
  * progressive handle's sums are not, so the next rt_render overwrites the result. */
 int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float floor, void* stream);
+/* Adds a W*H float[4] layer (rt_render_indirect's dev_layer, carried and filtered
+ * or not) into W*H packed RGBA8 pixels in place, one pass.  For each of R, G and
+ * B, with c the frame's byte, a_k the albedo's byte and layer[k] the layer's
+ * channel:
+ *   k = dev_albedo ? (float)a_k * (1.0f / 255.0f) : 1.0f;
+ *   v = (float)c + ((k * gain) * layer[k]) * 255.0f;
+ * and the stored byte is (uint8_t)fminf(fmaxf(v, 0.0f), 255.0f): truncated like
+ * the frames' own conversion, a NaN stores 0.  A is unchanged and the layer's w
+ * is not read.  dev_albedo: W*H RGBA8 as rt_render_gbuffer wrote it (the surface
+ * that receives the light reflects it by its own colour), or NULL: white.
+ * dev_rgba8 NULL: the handle's internal framebuffer.  A bound display is never
+ * mapped: pass its mapped pointer.  gain NaN, infinite or negative, or a NULL
+ * layer: RT_E_INVALID.  Stream and ordering as rt_apply_layer; only the given
+ * buffer is modified. */
+int rt_add_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer4, const void* dev_albedo, float gain,
+                 void* stream);
 
 /* A per-pixel layer carried across camera motion: the running mean of a layer
  * (rt_render_ao's dev_ao at a few rays, salt = the frame number; a float4 radiance

@@ -251,6 +251,23 @@ public:
         const rt_ao_out o{dev_ao, dev_occluded};
         check(rt_render_ao(r_, &p, &o, stream, stats), r_);
     }
+    // one-bounce diffuse light layer of the current camera (rt_render_indirect):
+    // renderAO's rays to their nearest hits, each shaded as a frame shades it; W*H
+    // float[4] {r, g, b, open share} and W*H uint32 hit counts in device memory,
+    // each optional
+    void renderIndirect(uint32_t rays, float radius, void* dev_layer, void* dev_occluded = nullptr, uint32_t salt = 0,
+                        float sky_scale = 1.0f, void* stream = nullptr, rt_stats* stats = nullptr) {
+        const rt_indirect_params p{rays, radius, salt, sky_scale, 0u};
+        const rt_indirect_out o{dev_layer, dev_occluded};
+        check(rt_render_indirect(r_, &p, &o, stream, stats), r_);
+    }
+    // a W*H float[4] layer added into RGBA8 pixels in place (rt_add_layer), times
+    // gain and, with renderGBuffer's albedo, the pixel's albedo; dev_rgba8 null: the
+    // internal framebuffer
+    void addLayer(const void* dev_layer4, float gain = 1.0f, const void* dev_albedo = nullptr,
+                  void* dev_rgba8 = nullptr, void* stream = nullptr) {
+        check(rt_add_layer(r_, dev_rgba8, dev_layer4, dev_albedo, gain, stream), r_);
+    }
     // guide-driven filter of a per-pixel layer (rt_filter_layer): W*H*channels floats
     // from dev_in to dev_out, steered by renderGBuffer's hits and normals
     void filterLayer(const void* dev_in, void* dev_out, const void* dev_hits, const void* dev_normals,

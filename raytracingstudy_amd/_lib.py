@@ -231,6 +231,15 @@ class RtAoOut(ctypes.Structure):
     _fields_ = [("dev_ao", ctypes.c_void_p), ("dev_occluded", ctypes.c_void_p)]
 
 
+class RtIndirectParams(ctypes.Structure):
+    _fields_ = [("rays", ctypes.c_uint32), ("radius", ctypes.c_float), ("salt", ctypes.c_uint32),
+                ("sky_scale", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class RtIndirectOut(ctypes.Structure):
+    _fields_ = [("dev_layer", ctypes.c_void_p), ("dev_occluded", ctypes.c_void_p)]
+
+
 class RtFilterParams(ctypes.Structure):
     _fields_ = [("passes", ctypes.c_uint32), ("channels", ctypes.c_uint32), ("depth_sigma", ctypes.c_float),
                 ("normal_power", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -299,6 +308,9 @@ SIGNATURES = {
     "rt_pick_thick": (_int, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtHit), _fp]),
     "rt_render_gbuffer": (_int, [_P, ctypes.POINTER(RtGBuffer), _P, ctypes.POINTER(RtStats)]),
     "rt_render_ao": (_int, [_P, ctypes.POINTER(RtAoParams), ctypes.POINTER(RtAoOut), _P, ctypes.POINTER(RtStats)]),
+    "rt_render_indirect": (_int, [_P, ctypes.POINTER(RtIndirectParams), ctypes.POINTER(RtIndirectOut), _P,
+                                  ctypes.POINTER(RtStats)]),
+    "rt_add_layer": (_int, [_P, _P, _P, _P, ctypes.c_float, _P]),
     "rt_filter_params_default": (None, [ctypes.POINTER(RtFilterParams)]),
     "rt_filter_layer": (_int, [_P, ctypes.POINTER(RtFilterParams), ctypes.POINTER(RtGBuffer), _P, _P, _P,
                                ctypes.POINTER(RtStats)]),

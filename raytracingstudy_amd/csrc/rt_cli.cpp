@@ -10,6 +10,7 @@
 //          [--save-scene out.rtsph] [--host-build] [--gpus N [--same-device]]
 //          [--progressive] [--panel] [--walk] [--test-poison] [--gbuffer hits.bin]
 //          [--ao ao.pgm [--ao-rays R] [--ao-radius X] [--ao-filter PASSES]]
+//          [--indirect image.ppm [--indirect-rays R] [--indirect-radius X]]
 //
 // --panel prints the stats panel (rt_camera.hpp StatsPanel: the reference's
 // ImGui window numbers plus Mrays/s, spp, GPUs) after every frame; --walk
@@ -22,6 +23,10 @@
 // 255 = open.  --ao-filter PASSES (1..5) filters the layer under the G-buffer's
 // guides first (rt_filter_layer at its default tolerances) and writes the
 // filtered layer instead, (uint8)(value * 255).
+// --indirect renders that camera's one-bounce diffuse layer (rt_render_indirect;
+// R rays a pixel, default 4, of length X, default 0.25, sky_scale 1), adds it into
+// the last frame under the G-buffer's albedo (rt_add_layer, gain 1) and writes
+// the result as a PPM.
 //
 // --gpus N: one process drives N devices through the C-ABI's
 // multi-device handle (rt_create_multi): device k renders the 64x64 tiles
@@ -117,6 +122,9 @@ int main(int argc, char** argv) {
     std::string cfg = "c2", out, scene_in, scene_out, gbuffer_out, ao_out;
     int ao_rays = 16, ao_filter = 0;
     float ao_radius = 0.1f;
+    std::string indirect_out;
+    int indirect_rays = 4;
+    float indirect_radius = 0.25f;
     bool host_build = false, same_device = false, progressive = false, panel = false,
          walk = false, poison = false;
     int gpus = 1;
@@ -147,6 +155,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ao-rays")) ao_rays = atoi(next("--ao-rays"));
         else if (!strcmp(argv[i], "--ao-radius")) ao_radius = (float)atof(next("--ao-radius"));
         else if (!strcmp(argv[i], "--ao-filter")) ao_filter = atoi(next("--ao-filter"));
+        else if (!strcmp(argv[i], "--indirect")) indirect_out = next("--indirect");
+        else if (!strcmp(argv[i], "--indirect-rays")) indirect_rays = atoi(next("--indirect-rays"));
+        else if (!strcmp(argv[i], "--indirect-radius")) indirect_radius = (float)atof(next("--indirect-radius"));
         else if (!strcmp(argv[i], "--host-build")) host_build = true;
         else if (!strcmp(argv[i], "--gpus")) gpus = atoi(next("--gpus")), multi = true;
         else if (!strcmp(argv[i], "--same-device")) same_device = true;
@@ -219,6 +230,7 @@ int main(int argc, char** argv) {
             if (!scene) throw rtamd::Error(RT_E_INVALID, "--gpus needs a scene config");
             if (!gbuffer_out.empty()) throw rtamd::Error(RT_E_INVALID, "--gbuffer is single-device here");
             if (!ao_out.empty()) throw rtamd::Error(RT_E_INVALID, "--ao is single-device here");
+            if (!indirect_out.empty()) throw rtamd::Error(RT_E_INVALID, "--indirect is single-device here");
             return run_multi(rc, pose, gpus, same_device, frames, out, W, H, spp, depth, n,
                              scene_in);
         }
@@ -345,6 +357,37 @@ int main(int argc, char** argv) {
             printf("ao: %llu of %llu rays occluded (%d rays a pixel, radius %g), %.3f ms\n", total,
                    (unsigned long long)ast.shadow_rays, ao_rays, ao_radius, ast.ms);
             if (ao_filter) printf("ao-filter: %d passes, %.3f ms\n", ao_filter, fst.ms);
+        }
+        if (!indirect_out.empty()) {
+            // after the last frame: its image with the camera's one-bounce layer added (no reprojection, no filter)
+            if (!scene) throw rtamd::Error(RT_E_INVALID, "--indirect needs a scene config");
+            const size_t npix = (size_t)W * H;
+            struct DevBufs {
+                void* p[3] = {nullptr, nullptr, nullptr};
+                ~DevBufs() {
+                    for (void* q : p)
+                        if (q) (void)hipFree(q);
+                }
+            } d;
+            enum { kLayer, kOcc, kAlbedo };
+            const size_t bytes[3] = {npix * 4 * sizeof(float), npix * sizeof(uint32_t), npix * sizeof(uint32_t)};
+            for (int b = 0; b < 3; ++b)
+                if (hipMalloc(&d.p[b], bytes[b]) != hipSuccess)
+                    throw rtamd::Error(RT_E_HIP, "hipMalloc of the indirect buffers");
+            rt_stats ist{};
+            r.renderGBuffer(nullptr, nullptr, d.p[kAlbedo]);
+            r.renderIndirect((uint32_t)indirect_rays, indirect_radius, d.p[kLayer], d.p[kOcc], 0, 1.0f, nullptr, &ist);
+            r.addLayer(d.p[kLayer], 1.0f, d.p[kAlbedo]);
+            std::vector<uint8_t> img(npix * 4);
+            r.readback(img.data());
+            std::vector<uint32_t> occ(npix);
+            if (hipMemcpy(occ.data(), d.p[kOcc], bytes[kOcc], hipMemcpyDeviceToHost) != hipSuccess)
+                throw rtamd::Error(RT_E_HIP, "hipMemcpy of the hit counts");
+            unsigned long long total = 0;
+            for (size_t i = 0; i < npix; ++i) total += occ[i];
+            if (write_ppm(indirect_out, img, W, H)) return 1;
+            printf("indirect: %llu bounce rays hit, %llu bounce and shadow rays cast (%d rays a pixel, radius %g), %.3f ms\n",
+                   total, (unsigned long long)ist.shadow_rays, indirect_rays, indirect_radius, ist.ms);
         }
     } catch (const rtamd::Error& e) {
         fprintf(stderr, "rt_cli: %s (code %d)\n", e.what(), e.code);

@@ -1,6 +1,6 @@
 // rt_filter.hip — the guide-driven filter of a per-pixel layer (rt_filter_layer)
 // and the multiply of a layer into an RGBA8 frame (rt_apply_layer); include/rt.h,
-// DESIGN.md 5.16.  The reference has no counterpart: its render kernel writes one
+// DESIGN.md 5.16; and a float4 layer added into one (rt_add_layer, 5.18).  The reference has no counterpart: its render kernel writes one
 // colour per pixel (src/renderer.cu:57-82).
 //
 // The filter is an edge-avoiding a-trous wavelet filter: per pass 25 taps of a
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_filter_math.h"
+#include "rt_indirect_math.h"  // add_layer_pixel
 #include "rt_layer.h"  // LayerPixel: a layer's pixel as one dword or one dwordx4
 #include "rt_params.h"
 
@@ -170,6 +171,19 @@ __global__ void __launch_bounds__(kFlatThreads) apply_layer_kernel(uint32_t* rgb
                (scale_channel((p >> 16) & 0xFFu, m) << 16) | (p & 0xFF000000u);
 }
 
+// A float4 layer's r, g and b added into the frame's bytes (rt_add_layer;
+// rt_indirect_math.h add_layer_pixel), each times gain and, with an albedo buffer,
+// the pixel's albedo byte / 255; the layer's w is not read, A is kept.
+template <bool kAlbedo>
+__global__ void __launch_bounds__(kFlatThreads) add_layer_kernel(uint32_t* rgba8, const float* layer,
+                                                                 const uint32_t* albedo, size_t n, float gain) {
+    const size_t i = static_cast<size_t>(blockIdx.x) * kFlatThreads + threadIdx.x;
+    if (i >= n) return;
+    LayerPixel<4> v;
+    v.load(layer, i);
+    rgba8[i] = add_layer_pixel(rgba8[i], v.v, kAlbedo ? albedo[i] : 0u, kAlbedo, gain);
+}
+
 // one pass: from the LDS image up to tap spacing kFilterLdsMaxStep, from global memory beyond
 template <uint32_t kC>
 void launch_pass(dim3 grid, dim3 block, hipStream_t st, const float4* rec, const float* src, float* dst, uint32_t W,
@@ -229,6 +243,20 @@ hipError_t launch_apply_layer(uint32_t* rgba8, const float* layer, uint32_t W, u
     const uint32_t blocks = static_cast<uint32_t>((n + kFlatThreads - 1u) / kFlatThreads);
     hipLaunchKernelGGL(apply_layer_kernel, dim3(blocks), dim3(kFlatThreads), 0, st, rgba8, layer, n, floor,
                        1.0f - floor);
+    return hipGetLastError();
+}
+
+// rgba8: W*H packed pixels, modified in place; layer4: W*H float4; albedo: W*H packed RGBA8, or null (white)
+hipError_t launch_add_layer(uint32_t* rgba8, const void* layer4, const uint32_t* albedo, uint32_t W, uint32_t H,
+                            float gain, hipStream_t st) {
+    if (W == 0 || H == 0) return hipSuccess;
+    const size_t n = static_cast<size_t>(W) * H;
+    const uint32_t blocks = static_cast<uint32_t>((n + kFlatThreads - 1u) / kFlatThreads);
+    const float* layer = static_cast<const float*>(layer4);
+    if (albedo)
+        hipLaunchKernelGGL((add_layer_kernel<true>), dim3(blocks), dim3(kFlatThreads), 0, st, rgba8, layer, albedo, n, gain);
+    else
+        hipLaunchKernelGGL((add_layer_kernel<false>), dim3(blocks), dim3(kFlatThreads), 0, st, rgba8, layer, albedo, n, gain);
     return hipGetLastError();
 }
 

@@ -8,6 +8,19 @@ using namespace rtamd;
 
 namespace rtamd {
 
+// The handle's shading as a kernel reads it (the frames, and the one-bounce layer
+// that shades its hits like them): the unit vector toward the light, the ambient
+// term and whether lit hits cast a shadow ray.
+void fill_shading(const rt_renderer* r, FrameArgs& a) {
+    a.shadows = (r->cfg.flags & RT_FLAG_NO_SHADOWS) ? 0u : 1u;
+    const float* ld = r->cfg.light_dir;
+    const float ll = sqrtf(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
+    a.L[0] = -(ld[0] / ll);
+    a.L[1] = -(ld[1] / ll);
+    a.L[2] = -(ld[2] / ll);
+    a.ambient = r->cfg.ambient;
+}
+
 void fill_frame_args(rt_renderer* r, FrameArgs& a) {
     memset(&a, 0, sizeof(a));
     fill_camera(r, a.cam);
@@ -20,14 +33,8 @@ void fill_frame_args(rt_renderer* r, FrameArgs& a) {
     if (r->cfg.flags & RT_FLAG_JITTER) jitter = true;
     if (r->cfg.flags & RT_FLAG_NO_JITTER) jitter = false;
     a.jitter = jitter ? 1u : 0u;
-    a.shadows = (r->cfg.flags & RT_FLAG_NO_SHADOWS) ? 0u : 1u;
     a.contract = (r->cfg.flags & RT_FLAG_COMPAT_FMA) ? 1u : 0u;
-    const float* ld = r->cfg.light_dir;
-    const float ll = sqrtf(ld[0] * ld[0] + ld[1] * ld[1] + ld[2] * ld[2]);
-    a.L[0] = -(ld[0] / ll);
-    a.L[1] = -(ld[1] / ll);
-    a.L[2] = -(ld[2] / ll);
-    a.ambient = r->cfg.ambient;
+    fill_shading(r, a);
     a.inv_spp = 1.0f / static_cast<float>(a.spp);
     if ((r->cfg.flags & RT_FLAG_PROGRESSIVE) && r->cfg.mode == RT_MODE_SCENE) {
         // frame k traces samples [k*spp, (k+1)*spp) and adds them onto the

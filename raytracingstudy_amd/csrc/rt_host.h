@@ -7,7 +7,8 @@
 //                 scene frame once, FramePlan, and hands the plan to them), tiles
 //   rt_bins_host.cpp  do_render's screen-bin step, the bin exports
 //   rt_queries.cpp    ray, multi-hit, overlap, closest-sphere and swept-sphere queries, picking, the G-buffer,
-//                     the AO layer, the layer filter, the layer multiply and the layer reprojection
+//                     the AO layer, the one-bounce layer, the layer filter, the layer multiply, the layer add and
+//                     the layer reprojection
 //   rt_multi.cpp  the multi-device handle and its RCCL loader
 #pragma once
 #include <hip/hip_runtime.h>
@@ -86,6 +87,11 @@ hipError_t launch_gbuffer(const FrameArgs& a, void* hits, void* normals, void* a
 // of length `radius` per hit pixel, directions keyed by `key` (rt_ao_math.h ao_key); null buffers are skipped
 hipError_t launch_ao(const FrameArgs& a, void* ao, void* occluded, uint32_t rays, float radius, uint32_t key,
                      unsigned long long* counters, hipStream_t st);
+// rt_indirect.hip: the one-bounce diffuse layer of a.cam at a.W x a.H against a.sc (prim_al made), shaded with a.L,
+// a.ambient and a.shadows: rt_ao.hip's `rays` rays to their nearest hits within `radius`, an escaped ray bringing
+// sky_scale times the frames' miss colour; W*H float4 {r, g, b, open share} and W*H hit counts, null buffers skipped
+hipError_t launch_indirect(const FrameArgs& a, void* layer, void* occluded, uint32_t rays, float radius, uint32_t key,
+                           float sky_scale, unsigned long long* counters, hipStream_t st);
 // rt_filter.hip: the guide-driven filter of a W x H layer of `channels` floats a pixel (rt_filter_math.h: the
 // parameters, which the caller checked, and the pass plan): packs hits and normals into `rec` (W*H), then `passes`
 // passes from `in` to `out` through `pong` (as large as the layer; may be null for one pass)
@@ -95,6 +101,10 @@ hipError_t launch_filter(uint32_t W, uint32_t H, const void* hits, const void* n
 // ... and the multiply of a W x H layer into packed RGBA8 pixels in place: m = floor + (1 - floor) * layer
 hipError_t launch_apply_layer(uint32_t* rgba8, const float* layer, uint32_t W, uint32_t H, float floor,
                               hipStream_t st);
+// ... and a W x H float4 layer's r, g, b added into packed RGBA8 pixels in place, times `gain` and (albedo != null) the
+// pixel's albedo bytes / 255 (rt_indirect_math.h add_layer_pixel)
+hipError_t launch_add_layer(uint32_t* rgba8, const void* layer4, const uint32_t* albedo, uint32_t W, uint32_t H,
+                            float gain, hipStream_t st);
 // rt_reproject.hip: a W x H layer of `channels` floats a pixel carried from the previous camera `prev` into `cam`
 // (rt_reproject_math.h: the parameters, which the caller checked): `hits` and `cur` of the current frame to `out` and
 // `count_out`; h_hits, h_layer and h_count the previous frame's, h_hits null for no history
@@ -469,6 +479,7 @@ void occ_collect_time(rt_renderer* r);
 int build_scene(rt_renderer* r);
 // rt_frame.cpp
 void fill_frame_args(rt_renderer* r, FrameArgs& a);
+void fill_shading(const rt_renderer* r, FrameArgs& a);  // a.L, a.ambient, a.shadows of the handle's config
 int do_render(rt_renderer* r, FrameArgs& a, void* stream, rt_stats* stats);
 int ensure_prim_al(rt_renderer* r, SceneArgs& sc, hipStream_t st);
 int check_tiles(rt_renderer* r, const uint32_t* ids, uint32_t n_tiles, uint32_t ts,

@@ -1,7 +1,7 @@
 // rt_queries.cpp — the calls that read a scene without rendering a frame
 // (DESIGN.md 5.7): ray, multi-hit, sphere-overlap, closest-sphere and
-// swept-sphere queries, their single-item wrappers, the first-hit G-buffer and the
-// ambient-occlusion layer.  The reference has none
+// swept-sphere queries, their single-item wrappers, the first-hit G-buffer, the
+// ambient-occlusion layer and the one-bounce diffuse layer.  The reference has none
 // (Octree::traverse is a stub, include/octree.h:19-21; its render kernel
 // writes one colour per pixel, src/renderer.cu:57-82).  A query reads scene
 // (the G-buffer and the AO layer: and camera) state only: it takes no frame id, leaves the
@@ -10,11 +10,12 @@
 // checks its own arguments in its own order (rt.h states the codes); what
 // follows the checks is stated once, in query_begin and query_launch.  The
 // layer calls at the end (rt_filter_layer, rt_apply_layer; DESIGN.md 5.16;
-// rt_reproject_layer, 5.17) read no scene at all, only the handle's size and,
+// rt_add_layer, 5.18; rt_reproject_layer, 5.17) read no scene at all, only the handle's size and,
 // the last, its camera; they share the stream ordering and the stats bracket.
 #include "rt_ao_math.h"
 #include "rt_filter_math.h"
 #include "rt_host.h"
+#include "rt_indirect_math.h"
 
 using namespace rtamd;
 
@@ -441,6 +442,49 @@ int rt_render_ao(rt_renderer* r, const rt_ao_params* p, const rt_ao_out* out, vo
     return st;
 }
 
+// The one-bounce diffuse layer of the current camera:
+// rt_render_ao's rays to their nearest hits, each hit shaded as a frame shades it
+// (fill_shading: the frames' own L, ambient and shadow switch), and like it no
+// fill_frame_args and nothing of the frames' framebuffer.
+int rt_render_indirect(rt_renderer* r, const rt_indirect_params* p, const rt_indirect_out* out, void* stream,
+                       rt_stats* stats) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_render_indirect: null handle");
+    if (!p) return fail(r, RT_E_INVALID, "rt_render_indirect: null parameters");
+    if (!out || (!out->dev_layer && !out->dev_occluded))
+        return fail(r, RT_E_INVALID, "rt_render_indirect: no output buffer");
+    if (!ao_rays_ok(p->rays))
+        return fail(r, RT_E_INVALID, "rt_render_indirect: rays must be 1, 2, 4, 8, 16, 32 or 64");
+    if (!ao_radius_ok(p->radius)) return fail(r, RT_E_INVALID, "rt_render_indirect: radius must be > 0");
+    if (!indirect_scale_ok(p->sky_scale))
+        return fail(r, RT_E_INVALID, "rt_render_indirect: sky_scale must be finite and >= 0");
+    if (p->flags) return fail(r, RT_E_INVALID, "rt_render_indirect: unknown flag bits");
+    if (!r->has_scene) return fail(r, RT_E_NOSCENE, "rt_render_indirect: no scene (rt_set_scene first)");
+    hipStream_t hs;
+    FrameArgs a;
+    int st;
+    if ((st = query_begin(r, stream, hs, a))) return st;
+    fill_camera(r, a.cam);
+    a.W = r->W;
+    a.H = r->H;
+    fill_shading(r, a);
+    // the frames' own albedo table, made ahead of the stats bracket like the G-buffer's
+    if ((st = ensure_prim_al(r, a.sc, hs))) return st;
+    const uint32_t key = ao_key(mix32(r->cfg.seed ^ 0x9E3779B9u), p->salt);
+    st = query_launch(r, "rt_render_indirect", hs, stats, [&](unsigned long long* ctr) {
+        return launch_indirect(a, out->dev_layer, out->dev_occluded, p->rays, p->radius, key, p->sky_scale, ctr, hs);
+    });
+    if (!st && stats) {
+        stats->primary_rays = static_cast<uint64_t>(r->W) * r->H;
+        // the bounce rays and the shadow rays at their hits are the kernel's count, word 1 of the
+        // stat lines query_launch just read (rt_render_ao's way)
+        unsigned long long lines[kStatLineWords], c[4];
+        RT_HIP(r, hipMemcpy(lines, r->q.counters.p, sizeof(lines), hipMemcpyDeviceToHost));
+        sum_stat_lines(lines, c);
+        stats->shadow_rays = c[1];
+    }
+    return st;
+}
+
 void rt_filter_params_default(rt_filter_params* p) {
     if (!p) return;
     p->passes = 3;
@@ -494,6 +538,23 @@ int rt_apply_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer, float
     if ((st = stream_begin(r, stream, hs))) return st;
     return query_launch(r, "rt_apply_layer", hs, nullptr, [&](unsigned long long*) {
         return launch_apply_layer(px, static_cast<const float*>(dev_layer), r->W, r->H, floor, hs);
+    });
+}
+
+// A float4 layer's r, g and b added into a frame's pixels, in place (DESIGN.md
+// 5.18): rt_apply_layer's buffers, stream and ordering.
+int rt_add_layer(rt_renderer* r, void* dev_rgba8, const void* dev_layer4, const void* dev_albedo, float gain,
+                 void* stream) {
+    if (!r) return fail(r, RT_E_INVALID, "rt_add_layer: null handle");
+    if (!dev_layer4) return fail(r, RT_E_INVALID, "rt_add_layer: null layer");
+    if (!indirect_scale_ok(gain)) return fail(r, RT_E_INVALID, "rt_add_layer: gain must be finite and >= 0");
+    uint32_t* px = dev_rgba8 ? static_cast<uint32_t*>(dev_rgba8) : r->fb.p;
+    if (!px) return fail(r, RT_E_STATE, "rt_add_layer: no framebuffer (a resize failed): resize again");
+    hipStream_t hs;
+    int st;
+    if ((st = stream_begin(r, stream, hs))) return st;
+    return query_launch(r, "rt_add_layer", hs, nullptr, [&](unsigned long long*) {
+        return launch_add_layer(px, dev_layer4, static_cast<const uint32_t*>(dev_albedo), r->W, r->H, gain, hs);
     });
 }
 

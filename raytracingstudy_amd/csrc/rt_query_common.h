@@ -1,5 +1,5 @@
 // rt_query_common.h — what the query units (rt_query.hip, rt_multihit.hip,
-// rt_overlap.hip, rt_closest.hip, rt_sweep.hip, rt_gbuffer.hip, rt_ao.hip) share: the stats launches' wave
+// rt_overlap.hip, rt_closest.hip, rt_sweep.hip, rt_gbuffer.hip, rt_ao.hip, rt_indirect.hip) share: the stats launches' wave
 // sum and the visiting-order permutation of a child mask on the device, and the launchers' grid,
 // stack size and k dispatch on the host.  rt_descent.h holds what the overlap, closest and sweep
 // units share beyond that: their descent, leaf scan and stack levels.

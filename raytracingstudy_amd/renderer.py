@@ -718,6 +718,54 @@ class KernelRenderer:
             out["stats"] = st
         return out
 
+    # -- one-bounce diffuse light layer (rt_render_indirect, rt_add_layer) -------------------
+    def render_indirect_device(self, rays: int, radius: float, layer_ptr: Optional[int] = None,
+                               occluded_ptr: Optional[int] = None, salt: int = 0, sky_scale: float = 1.0,
+                               stream: Optional[int] = None, stats: bool = False) -> Optional[RtStats]:
+        """rt_render_indirect into buffers already on the GPU, each optional, in frame
+        layout (pixel y*W + x): W*H float32[4] {r, g, b, open share} at layer_ptr
+        (16-byte aligned; a miss {0, 0, 0, 1}), W*H uint32 counts of the bounce rays
+        that hit at occluded_ptr.  `rays` (1, 2, 4, .. 64) nearest-hit rays of length
+        `radius` from every hit pixel, render_ao_device's rays under the same salt;
+        each hit is shaded as a frame shades it, an escaped ray brings sky_scale
+        times the frames' miss colour.  Asynchronous on `stream` (None: the
+        renderer's own) unless stats."""
+        p = _lib.RtIndirectParams(int(rays), float(radius), int(salt) & 0xFFFFFFFF, float(sky_scale), 0)
+        o = _lib.RtIndirectOut(layer_ptr or None, occluded_ptr or None)
+        st, st_arg = _stats_arg(stats)
+        check(self._lib.rt_render_indirect(self._h, ctypes.byref(p), ctypes.byref(o), _ptr(stream), st_arg), self._h)
+        return st
+
+    def render_indirect(self, rays: int, radius: float, salt: int = 0, sky_scale: float = 1.0,
+                        stats: bool = False) -> dict:
+        """The one-bounce diffuse layer of the current size and camera as host arrays:
+        {"layer": (H, W, 4) float32, "occluded": (H, W) uint32[, "stats": RtStats]}.
+        layer[..., :3] is the mean light the bounce rays bring, layer[..., 3] the
+        share of them that escaped (render_ao's "ao" under the same parameters)."""
+        import torch
+        w, h = self.width, self.height
+        dev = torch.device("cuda", self.multi_info()["devices"][0])
+        d_layer = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        d_occ = torch.empty((h, w), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the allocations are torch's
+        st = self.render_indirect_device(rays, radius, d_layer.data_ptr(), d_occ.data_ptr(), salt, sky_scale, None,
+                                         stats)
+        self.synchronize()
+        out = {"layer": d_layer.cpu().numpy(), "occluded": d_occ.cpu().numpy().view(np.uint32)}
+        if stats:
+            out["stats"] = st
+        return out
+
+    def add_layer_device(self, layer_ptr: int, gain: float = 1.0, albedo_ptr: Optional[int] = None,
+                         rgba8_ptr: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """rt_add_layer: the W*H float32[4] layer at layer_ptr added into the W*H RGBA8
+        pixels at rgba8_ptr (None: the internal framebuffer) in place, r, g and b
+        times gain and, with render_gbuffer_device's albedo at albedo_ptr, times the
+        pixel's albedo; alpha is kept, the layer's w is not read.  Asynchronous on
+        `stream`."""
+        check(self._lib.rt_add_layer(self._h, _ptr(rgba8_ptr), _ptr(layer_ptr), _ptr(albedo_ptr), float(gain),
+                                     _ptr(stream)), self._h)
+
     # -- guide-driven layer filter and layer multiply (rt_filter_layer, rt_apply_layer) ----
     def filter_layer_device(self, in_ptr: int, out_ptr: int, hits_ptr: int, normals_ptr: int, passes: int = 3,
                             channels: int = 1, depth_sigma: float = 0.05, normal_power: int = 5,
